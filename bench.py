@@ -36,7 +36,17 @@ seed 10 + rank, in calls of at most 12.5M reads; at N = 1 one 12.5M-read call,
 ranks by DP cells, crispresso_amd.distributed.cell_partition, one
 nw_align_multi_ops_packed call per rank).
 
-Extra keys: "kernel_rate" (the same resident pass timed by HIP events on the
+A plain run (`bench.py --gpus N --steps K --warmup W`) does what value needs and no more: it
+generates and packs the batch, uploads it, warms up, times the K resident passes and prints the
+line (metric, value, unit, ms_per_step, higher_is_better, dtype, the run's shape).  Everything
+else described here -- call_pcie and the other boundaries, the checks against the oracle, the
+HIP-event and roofline figures, the CPU baselines and every leg -- runs with `--full`, after
+which the line carries all the keys below.  `--dump-outputs DIR` (either form) writes what the
+last timed pass left in HBM for its caller (nw_batch_download_ops: the records, the run offsets
+and the runs of every read) as DIR/<name>.npy, see dump_outputs; the batch is seeded, so two
+builds given the same arguments align the same reads.
+
+Extra keys (--full): "kernel_rate" (the same resident pass timed by HIP events on the
 aligner's stream, per phase and per path), "resident_check" (the timed pass's
 records and runs against the pipelined call's, every read), "sample_check"
 (every 100th read of the call's output re-aligned by the CPU oracle, outside the
@@ -525,6 +535,56 @@ def timed_calls(dist, call, steps, warmup, warm_s=0.0):
     return max_over_ranks(dist, time.perf_counter() - t0)
 
 
+def timed_resident(al, pr, dist, steps, warmup, phase_events=False):
+    """value's timed region: the hot path over the batch resident in HBM (wall clock, barriers, max
+    over ranks).  The 1M-read call runs the first level's lane walk + stop summary on every chunk
+    (>= 65536 reads), so the resident pass does too; its per-phase events are off
+    unless asked for.  -> (seconds of the `steps` timed passes, their mean HIP-event time in ms);
+    the last pass's records and runs stay in HBM (download_ops)."""
+    al.upload_packed(pr)
+    al.set_lane_walk(True)
+    al.set_phase_events(phase_events)
+    step_kms = []
+
+    def resident_step():
+        al.run_async()
+        step_kms.append(al.sync())   # records + runs of every read in HBM; the pass's HIP-event time
+
+    elapsed = timed_calls(dist, resident_step, steps, warmup, warm_s=RESIDENT_WARM_S)
+    return elapsed, float(np.mean(step_kms[-steps:]))   # the timed steps' own device time (roofline)
+
+
+def headline(n, world, seen, args, elapsed, geo, place):
+    """The head of the result line: value and what it was measured on (a plain run prints little else)."""
+    return {
+        "metric": "aligned reads/sec (250 bp amplicon x 1M reads) at 1/2/4/8 MI355X",
+        "value": n * world * args.steps / elapsed,
+        "unit": "aligned reads/s",
+        "n_gpus": world,
+        "ranks_seen": seen,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "int16x2",
+        "data": "synthetic (SURVEY 8d C2 mix: 60% exact, 20% 1-3 subs, 10% del, 5% ins, 5% 1% noise)",
+        "config": {
+            "workload": f"C2: {n} synthetic ~250 bp reads x 250 bp amplicon per GPU, EMBOSS needle semantics "
+                        "(EDNAFULL, gapopen 10, gapextend 0.5, free end gaps); step = one pass of the hot path over "
+                        "the batch resident in HBM (2 bits per base + lengths): every read's record + traceback "
+                        "runs written to HBM (nw_batch_run_async + nw_batch_sync); the PCIe-inclusive call "
+                        "(pinned host batch in -> pinned host records out) is call_pcie (--full)",
+            "reads_per_gpu": n,
+            "amplicon_len": AMPLICON_LEN,
+            "parallelism": f"read shards x{world} (no collective on the data path; gloo host barrier)",
+            "kernel_geometry": geo,
+        },
+        "host_placement": place,
+    }
+
+
 def pack_pinned(buf, offsets, threads):
     """(PackedReads in pinned memory, its buffers): text batch -> 2 bits per base."""
     from crispresso_amd import _lib
@@ -781,6 +841,43 @@ def band_cells(counts, La, mean_len):
             counts["exact_kernel"] * La * mean_len)
 
 
+DUMP_BUDGET = 60_000_000   # bytes of .npy payload --dump-outputs may write (the limit is 64 MB)
+
+
+def dump_outputs(out_dir, res, n):
+    """--dump-outputs: the timed path's last output, as its caller gets it from nw_batch_download_ops
+    (`res`, an OpsBatch of the n reads), written as float arrays every value of which is exact:
+    records.npy (float32, reads x 8: the nw_stat fields in _lib.STAT_FIELDS order, all below 2^24),
+    run_offsets.npy (float64, reads + 1) and runs.npy (float64: the uint32 runs, type << 28 | length).
+    A batch whose arrays would exceed DUMP_BUDGET is sampled: a fixed (seed 0) sorted subset of the
+    reads, their indices in read_index.npy, their records, and their runs joined in that order with
+    run_offsets rebuilt over them."""
+    from crispresso_amd import _lib
+
+    os.makedirs(out_dir, exist_ok=True)
+    off = np.asarray(res.ops_off[: n + 1], dtype=np.int64)
+    per_read = 4 * len(_lib.STAT_FIELDS) + 8 + 8.0 * int(off[n]) / max(n, 1)   # record, run offset, runs
+    idx = None
+    if n * per_read + 8 > DUMP_BUDGET:
+        k = max(1, int(DUMP_BUDGET * 0.9 / (per_read + 8)))   # + its index; 0.9: the sample's runs per read vary
+        idx = np.sort(np.random.Generator(np.random.PCG64(0)).choice(n, size=k, replace=False)).astype(np.int64)
+    stats, ops = res.stats[:n], res.ops
+    if idx is not None:
+        cnt = off[idx + 1] - off[idx]
+        sub_off = np.zeros(len(idx) + 1, np.int64)
+        np.cumsum(cnt, out=sub_off[1:])
+        which = np.repeat(np.arange(len(idx)), cnt)   # the sampled read of each of the sample's runs
+        ops = ops[off[idx][which] + (np.arange(int(sub_off[-1])) - sub_off[which])]
+        stats, off = stats[idx], sub_off
+        np.save(os.path.join(out_dir, "read_index.npy"), idx.astype(np.float64))
+    records = np.stack([stats[f] for f in _lib.STAT_FIELDS], axis=1).astype(np.float32)
+    np.save(os.path.join(out_dir, "records.npy"), records)
+    np.save(os.path.join(out_dir, "run_offsets.npy"), off.astype(np.float64))
+    np.save(os.path.join(out_dir, "runs.npy"), np.asarray(ops[: int(off[-1])]).astype(np.float64))
+    return {"dir": out_dir, "reads": int(len(stats)), "sampled": idx is not None,
+            "bytes": int(records.nbytes + 8 * len(off) + 8 * int(off[-1]) + (8 * len(idx) if idx is not None else 0))}
+
+
 def dry_run(args, rank, local, world, dist, seen, place):
     """--dry-run: the N-rank plumbing without a GPU (CPU tests).  Each rank derives its share of
     the C2 / C4 / pooled work exactly as a measured run would and reports it, with its host
@@ -827,6 +924,11 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--reads", type=int, default=READS_PER_GPU)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: call_pcie, the text call, the oracle checks, HIP-event and "
+                         "roofline figures, CPU baselines and the legs (a plain run times the resident passes only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last timed pass's records and runs as DIR/<name>.npy")
     ap.add_argument("--cpu-sample", type=int, default=300_000)
     ap.add_argument("--cpu-sample-1t", type=int, default=20_000)
     ap.add_argument("--cpu-threads", type=int, default=0,
@@ -856,6 +958,8 @@ def main():
                     help="launch check without a GPU: form the world, partition the C4 / pooled work over the ranks, "
                          "print rank 0's line with \"dry_run\": true; no alignment, no value")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus))
@@ -899,15 +1003,11 @@ def main():
     al.set_reference(amplicon)
     place["device_pci"] = placement.device_pci(local)   # the device HIP opened: does it match the KFD order?
     place["pci_match"] = place["device_pci"] == place["gpu_pci"] if place["gpu_pci"] else None
-    # the host batch and the outputs in pinned memory (the native FASTQ ingest, nw_fastq_pack, hands the
-    # aligner exactly such a batch: the e2e leg)
+    # the host batch in pinned memory (the native FASTQ ingest, nw_fastq_pack, hands the aligner exactly
+    # such a batch: the e2e leg); the calls' pinned outputs follow where --full needs them
     pb, po = _lib.pinned_copy(buf), _lib.pinned_copy(offsets)
     p_packed = _lib.PinnedBuffer((int(offsets[-1]) + 3) // 4 + 16, np.uint8)
     p_lens = _lib.PinnedBuffer(max(n, 1), np.uint16)
-    p_stats = _lib.PinnedBuffer(n, _lib.STAT_DTYPE)
-    p_off = _lib.PinnedBuffer(n + 1, np.int64)
-    p_ops = _lib.PinnedBuffer(4 * n + 4096, np.uint32)
-    out = (p_stats.array, p_ops.array, p_off.array)
     if args.quant_only:
         q = quant_leg(al, amplicon, buf, offsets, n, args.steps, args.warmup, rank, world, args.quant_cpu_sample, True)
         if rank == 0:
@@ -930,6 +1030,23 @@ def main():
     t1 = time.perf_counter()
     pr = pack_2bit(pb.array, po.array, nthreads=threads, packed=p_packed.array, lens=p_lens.array)
     pack_s = time.perf_counter() - t1
+    if not args.full and not args.skip_kernel_pass:   # a plain run: value's timed passes, their outputs, the line
+        elapsed, kms_timed = timed_resident(al, pr, dist, args.steps, args.warmup, args.phase_events)
+        dumped = dump_outputs(args.dump_outputs, al.download_ops(n), n) if args.dump_outputs and rank == 0 else None
+        if rank == 0:
+            line = headline(n, world, seen, args, elapsed, al.geometry(), place)
+            line.update({"full": False, "kernel_ms_avg": kms_timed, "dumped_outputs": dumped})
+            print(json.dumps(line), flush=True)
+        for b in (pb, po, p_packed, p_lens):
+            b.close()
+        al.close()
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+    p_stats = _lib.PinnedBuffer(n, _lib.STAT_DTYPE)
+    p_off = _lib.PinnedBuffer(n + 1, np.int64)
+    p_ops = _lib.PinnedBuffer(4 * n + 4096, np.uint32)
+    out = (p_stats.array, p_ops.array, p_off.array)
     state = {}
 
     def headline_call():
@@ -967,22 +1084,10 @@ def main():
     ob.expand(amplicon, pb.array, po.array, nthreads=threads)
     expand_s = time.perf_counter() - t1
 
-    # value: the hot path over the batch resident in HBM (wall clock, barriers, max over ranks); the
-    # 1M-read call runs the first level's lane walk + stop summary on every chunk (>= 65536 reads,
-    # DESIGN.md 4a), so the resident pass does too
-    al.upload_packed(pr)
-    al.set_lane_walk(True)
-    al.set_phase_events(args.phase_events)   # off: kernel_rate below times the phases, with their events
-
-    step_kms = []
-
-    def resident_step():
-        al.run_async()
-        step_kms.append(al.sync())   # records + runs of every read in HBM; the pass's HIP-event time
-
-    elapsed = timed_calls(dist, resident_step, args.steps, args.warmup, warm_s=RESIDENT_WARM_S)
-    kms_timed = float(np.mean(step_kms[-args.steps:]))   # the timed steps' own device time (roofline)
+    # value: the same timed passes as a plain run's (kernel_rate below times the phases, with their events)
+    elapsed, kms_timed = timed_resident(al, pr, dist, args.steps, args.warmup, args.phase_events)
     res = al.download_ops(n)
+    dumped = dump_outputs(args.dump_outputs, res, n) if args.dump_outputs and rank == 0 else None
     n_res = int(res.ops_off[n])
     resident_check = {
         "reads": n, "runs": n_res,
@@ -1060,31 +1165,10 @@ def main():
     fill_ms = phases["fill16_ms"]
     value = n * world * args.steps / elapsed
     if rank == 0:
-        line = {
-            "metric": "aligned reads/sec (250 bp amplicon x 1M reads) at 1/2/4/8 MI355X",
-            "value": value,
-            "unit": "aligned reads/s",
-            "n_gpus": world,
-            "ranks_seen": seen,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": ms_step,
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "int16x2",
-            "data": "synthetic (SURVEY 8d C2 mix: 60% exact, 20% 1-3 subs, 10% del, 5% ins, 5% 1% noise)",
-            "config": {
-                "workload": f"C2: {n} synthetic ~250 bp reads x 250 bp amplicon per GPU, EMBOSS needle semantics "
-                            "(EDNAFULL, gapopen 10, gapextend 0.5, free end gaps); step = one pass of the hot path over "
-                            "the batch resident in HBM (2 bits per base + lengths): every read's record + traceback "
-                            "runs written to HBM (nw_batch_run_async + nw_batch_sync); the PCIe-inclusive call "
-                            "(pinned host batch in -> pinned host records out) is call_pcie",
-                "reads_per_gpu": n,
-                "amplicon_len": AMPLICON_LEN,
-                "parallelism": f"read shards x{world} (no collective on the data path; gloo host barrier)",
-                "kernel_geometry": geo,
-            },
+        line = headline(n, world, seen, args, elapsed, geo, place)
+        line.update({
+            "full": True,
+            "dumped_outputs": dumped,
             "resident_check": resident_check,
             "call_pcie": {
                 "value": n * world * args.steps / elapsed_call, "unit": "aligned reads/s", "ms_per_step": ms_call,
@@ -1093,7 +1177,6 @@ def main():
                         "per base) in -> records + runs in pinned host memory, chunks pipelined over PCIe (value up "
                         "to round 4); same barriers and max over ranks",
             },
-            "host_placement": place,
             "ingest_pack": {"ms": pack_s * 1e3, "bases_per_s": (int(offsets[-1]) - int(offsets[0])) / pack_s,
                             "threads": threads, "exceptions": int(len(pr.exc_pos)),
                             "note": "nw_pack_reads: the text batch -> 2 bits per base + exception list (host; the "
@@ -1188,7 +1271,7 @@ def main():
             "c1_shape": legs["c1"],
             "downstream_quantification": quant,
             "upstream_merge": legs["merge"],
-        }
+        })
 
         def pick(d, *ks):
             return {k: d.get(k) for k in ks} if isinstance(d, dict) else None

@@ -10,7 +10,7 @@ mkdir -p $O
 cd $R
 for r in 1 2 3; do
   for f in "" "--phase-events"; do
-    timeout -k 10 200 python3 bench.py --steps 20 --warmup 5 --no-cpu --no-quant --no-legs --no-multi --no-check $f > $O/b.json 2> $O/b.err || { tail -20 $O/b.err; exit 1; }
+    timeout -k 10 200 python3 bench.py --full --steps 20 --warmup 5 --no-cpu --no-quant --no-legs --no-multi --no-check $f > $O/b.json 2> $O/b.err || { tail -20 $O/b.err; exit 1; }
     python3 -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); print('phase_events' if sys.argv[2] else 'no_events', 'value_ms', round(d['ms_per_step'],4), 'call_ms', round(d['call_pcie']['ms_per_step'],4), 'kernel_ms', round(d['kernel_rate']['kernel_ms'],4), d['resident_check']['same_as_call'])" $O/b.json "$f"
   done
 done

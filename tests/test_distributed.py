@@ -195,6 +195,33 @@ def test_multi_device_resident_second_pass():
     multi.close()
 
 
+def _shm_write_seconds(nbytes):
+    """Seconds the ranks take, between two barriers, to each write nbytes of its own into a fresh
+    shared-memory mapping with one plain copy: what the host's memory system gives a gather's
+    writers at this moment (page faults and the load of the host included)."""
+    import mmap
+    import time
+
+    src = np.ones(nbytes, np.uint8)
+    path = f"/dev/shm/crispr_gather_ref_{os.getpid()}"
+    fd = os.open(path, os.O_CREAT | os.O_EXCL | os.O_RDWR, 0o600)
+    try:
+        os.ftruncate(fd, nbytes)
+        mm = mmap.mmap(fd, nbytes)
+    finally:
+        os.close(fd)
+        os.unlink(path)
+    dst = np.ndarray(nbytes, np.uint8, buffer=mm)
+    dist.barrier()
+    t0 = time.perf_counter()
+    dst[...] = src
+    dist.barrier()
+    dt = time.perf_counter() - t0
+    del dst
+    mm.close()
+    return dt
+
+
 def _gather_worker(rank, world, port, out_dir, n, method):
     import time
 
@@ -215,10 +242,14 @@ def _gather_worker(rank, world, port, out_dir, n, method):
     np.cumsum(cnt, out=off[1:])
     ops = (np.arange(int(off[-1]), dtype=np.uint32) + np.uint32(7 * rank)) & np.uint32(0x3fffffff)
     mine = OpsBatch(stats, ops, off, rng.integers(220, 260, m).astype(np.int64), 2)
+    my_bytes = stats.nbytes + ops.nbytes + off.nbytes + mine.read_lens.nbytes
+    ref_dt = _shm_write_seconds(my_bytes) if method == "shm" else 0.0
     dist.barrier()
     t0 = time.perf_counter()
     res = _gather_ops(mine, dist, rank, world, method)
     dt = time.perf_counter() - t0
+    if method == "shm":   # the slower of the plain writes before and after the gather
+        ref_dt = max(ref_dt, _shm_write_seconds(my_bytes))
     if rank == 0:
         np.save(os.path.join(out_dir, "g_stats.npy"), res.stats)
         np.save(os.path.join(out_dir, "g_ops.npy"), res.ops)
@@ -226,7 +257,7 @@ def _gather_worker(rank, world, port, out_dir, n, method):
         np.save(os.path.join(out_dir, "g_lens.npy"), res.read_lens)
         nbytes = res.stats.nbytes + res.ops.nbytes + res.ops_off.nbytes + res.read_lens.nbytes
         with open(os.path.join(out_dir, "g_rate.txt"), "w") as f:
-            f.write(f"{nbytes / dt / 1e9:.3f} {dt:.3f}")
+            f.write(f"{nbytes / dt / 1e9:.3f} {dt:.3f} {nbytes / ref_dt / 1e9 if ref_dt else 0.0:.3f}")
     else:
         assert res is None
     dist.barrier()
@@ -236,9 +267,14 @@ def _gather_worker(rank, world, port, out_dir, n, method):
 @pytest.mark.parametrize("method,n", [("shm", 10_000_000), ("p2p", 1_000_000)])
 def test_gather_records_and_runs_scales(tmp_path, method, n):
     """Rank 0 gathers 10M reads' records + runs (about 45 B per read, ~0.5 GB) of a world-2 job
-    without pickling: shared memory between the ranks of one host (1.9-2.2 GB/s in this container,
-    page faults dominating; the assertion keeps a 2x margin for a loaded host), tensors
-    point-to-point otherwise; the joined arrays equal the parts concatenated in read order."""
+    without pickling: shared memory between the ranks of one host (1.9-2.2 GB/s on an idle 8-CPU
+    host, page faults dominating), tensors point-to-point otherwise; the joined arrays equal the
+    parts concatenated in read order.  The rate is held against what the host gives at that moment:
+    the ranks writing the same bytes into fresh shared memory with one plain copy each, timed the
+    same way right before and right after the gather (the slower of the two).  The gather is that
+    write plus a 32-byte exchange and two barriers, so it keeps within 2x of it, on an idle host
+    (where this is the 1.0 GB/s floor the test had) as on a loaded one (where a fixed floor failed
+    at 0.39 GB/s)."""
     from crispresso_amd import _lib
     from crispresso_amd.aligner import OpsBatch
     from crispresso_amd.distributed import concat_ops
@@ -263,7 +299,7 @@ def test_gather_records_and_runs_scales(tmp_path, method, n):
     assert np.array_equal(np.load(tmp_path / "g_ops.npy"), want.ops)
     assert np.array_equal(np.load(tmp_path / "g_off.npy"), want.ops_off)
     assert np.array_equal(np.load(tmp_path / "g_lens.npy"), want.read_lens)
-    rate, secs = map(float, open(tmp_path / "g_rate.txt").read().split())
-    print(f"gather {method}: {rate:.2f} GB/s ({secs:.3f} s)")
+    rate, secs, ref_rate = map(float, open(tmp_path / "g_rate.txt").read().split())
+    print(f"gather {method}: {rate:.2f} GB/s ({secs:.3f} s); plain shared-memory write {ref_rate:.2f} GB/s")
     if method == "shm":
-        assert rate >= 1.0, rate
+        assert rate >= 0.5 * ref_rate, (rate, ref_rate)
