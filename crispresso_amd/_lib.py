@@ -60,6 +60,9 @@ QUANT_EXPORTS = (
 # Every symbol include/crispr_flash.h declares.
 FLASH_EXPORTS = ("nwf_merge_batch", "nwf_last_error")
 
+# Every symbol include/crispr_trim.h declares.
+TRIM_EXPORTS = ("nwt_trim_batch", "nwt_last_error")
+
 # Every symbol include/crispr_synth.h declares (bench / test input generator).
 SYNTH_EXPORTS = ("nw_synth_offsets", "nw_synth_reads")
 NWF_COMBINED, NWF_OUTIE = 1, 2
@@ -69,6 +72,12 @@ class NwfParams(ctypes.Structure):
     """nwf_params (include/crispr_flash.h)."""
     _fields_ = [("min_overlap", c_int32), ("max_overlap", c_int32), ("max_mismatch_density", c_float),
                 ("allow_outies", c_int32), ("phred_offset", c_int32), ("cap_mismatch_quals", c_int32)]
+
+
+class NwtParams(ctypes.Structure):
+    """nwt_params (include/crispr_trim.h)."""
+    _fields_ = [("seed_mismatches", c_int32), ("palindrome_threshold", c_int32), ("simple_threshold", c_int32),
+                ("min_prefix", c_int32), ("keep_both", c_int32), ("minlen", c_int32)]
 
 
 class NwqParams(ctypes.Structure):
@@ -187,6 +196,10 @@ def load() -> ctypes.CDLL:
         "nwf_merge_batch": (c_int, [c_int, POINTER(NwfParams)] + [c_void_p] * 6 + [c_int64] + [c_void_p] * 4
                             + [POINTER(c_float)]),
         "nwf_last_error": (c_char_p, []),
+        "nwt_trim_batch": (c_int, [c_int, POINTER(NwtParams), c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                   c_void_p, c_int32] + [c_void_p] * 6 + [c_int64, c_void_p, c_void_p,
+                                                                          POINTER(c_float)]),
+        "nwt_last_error": (c_char_p, []),
         "nwq_create": (c_int, [c_int, POINTER(c_void_p)]),
         "nwq_destroy": (None, [ctx_p]),
         "nwq_last_error": (c_char_p, [ctx_p]),
@@ -241,7 +254,7 @@ def exported_symbols() -> dict:
     """Map of each declared symbol to whether the loaded library exports it."""
     lib = load()
     out = {}
-    for name in EXPORTS + QUANT_EXPORTS + FLASH_EXPORTS + SYNTH_EXPORTS:
+    for name in EXPORTS + QUANT_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + SYNTH_EXPORTS:
         try:
             getattr(lib, name)
             out[name] = name not in _MISSING
