@@ -351,6 +351,9 @@ class GpuAligner:
         ex = self.exact_reads()   # of the 16 / 32 levels' give-ups: the wide level certified the rest
         d["wide128"] = d["band_fallback"] - ex
         d["exact_kernel"] = ex
+        # of band_fallback: the wide level's reads of the first sweep, beside the 16-diagonal level
+        d["wide_first"] = (max(0, int(self.lib.nw_batch_wide_first_reads(self._h)))
+                           if _lib.has_symbol("nw_batch_wide_first_reads") else 0)   # (an older variant build)
         return d
 
     def device_output(self):

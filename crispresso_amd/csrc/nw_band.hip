@@ -656,6 +656,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
     const int m3 = a.band_maxsub, x3 = 4 * sc5, O3 = a.gap_open, D3 = 3 * (m3 + x3);
     const bool sub3_ok = !NW_NO_SUB3 && sub2_ok && x3 < m3 && 4 * m3 + O3 > D3 && 2 * m3 + 2 * O3 > D3 && 3 * O3 > D3 &&
                          m3 + 2 * O3 + (m3 + x3) > D3;
+    // Wide first (KernelArgs::wf_list): a plain read of the amplicon's length with k substitutions scores
+    // m La - (m + x) k on its main diagonal, and the 16-diagonal walk certifies an alignment only when
+    // its score exceeds m pmax - O, pmax the longest diagonal just outside the band (an equal-length
+    // pair: diagonals -7 .. 8, pmax = La - 8).  From (m + x) k >= m (La - pmax) + O on it cannot pass.
+    int wf_k = 0;   // 0: off
+    if (PK && a.wf_keys > 0 && a.ops && nd <= 64 && amp_acgt_all && a.amp2 && a.band_maxsub == 5 * sc5) {
+        int d16 = 0;
+        band_geometry2(La, La, La, &d16, 16);
+        const int outside = min(1 - d16, d16 + 16);   // La - pmax
+        wf_k = max(1, (a.band_maxsub * outside + a.gap_open + 9 * sc5 - 1) / (9 * sc5));
+    }
     const int lane = threadIdx.x & 63, wpb = blockDim.x >> 6;
     const unsigned tail_mask = (La & 3) ? (0xffffffffu >> (8 * (4 - (La & 3)))) : 0xffffffffu;
     const int sd = (int)(a.stride / 4);
@@ -715,6 +726,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
         unsigned long long pend3 = 0ull, pend_i = 0ull;   // queued for nw_band_cert (KernelArgs::cert_q)
         unsigned long long known = 0ull;   // copies of the known sequence (KernelArgs::known2)
         unsigned long long jog = 0ull;     // reads closer to the known sequence than to the amplicon (below)
+        unsigned long long wf_sub = 0ull;  // reads of the amplicon's length with wf_k substitutions or more
         // compare kCand candidates at a time (their loads in flight together); when the read
         // fits one 256-byte chunk (La <= 256) its exact copy's rows are written right
         // away from the words already in registers
@@ -739,6 +751,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
                 int k, f, f2, l;   // mismatches of the main diagonal, first, second and last base
                 main_diag_mism(rw, amp2s, La, &k, &f, &f2, &l);
                 exact = __ballot(c && k == 0);
+                wf_sub = __ballot(c && wf_k > 0 && k >= wf_k);
                 const bool s1 = c && sub1_ok && k == 1, s2 = c && sub2_ok && k == 2;
                 // diagonal d = sgn * sh (q <= La - 1 - sh): mismatches (counted up to 2), any at q >= qa, any at q <= qb
                 auto shifted = [&](int sgn, int sh, int qa, int qb, int* tot, bool* ge, bool* le) {
@@ -1131,12 +1144,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
             if (a.seed_info && r < r_end) a.seed_info[r] = sinfo;
             if (a.seed_info2 && r < r_end) a.seed_info2[r] = sinfo2;
         }
+        // wide first: a plain read (no exception byte, not a known sequence's variant) of another length
+        // than the amplicon's, or of its length with too many substitutions for the 16-diagonal band
+        const bool wf = wf_k > 0 && !exc && my_len > 0 && my_len <= a.band_lb_cap && !((jog >> lane) & 1ull) &&
+                        (my_len != La || ((wf_sub >> lane) & 1ull));
         if (r < r_end)
             a.sort_key[r] = (((exact | sub1 | sub2 | win | known) >> lane) & 1ull)
                                 ? a.band_lb_cap + 2
                                 : (sinfo ? a.band_lb_cap + 3 +
                                                min(a.seed_keys - 1, max(0, ((seed_dmin(sinfo) + seed_dmax(sinfo)) / 2 + La) >> 2))
-                                         : (my_len <= a.band_lb_cap && !((jog >> lane) & 1ull) ? my_len : a.band_lb_cap + 1));
+                                   : wf ? a.band_lb_cap + 3 + a.seed_keys + my_len
+                                        : (my_len <= a.band_lb_cap && !((jog >> lane) & 1ull) ? my_len : a.band_lb_cap + 1));
         if (a.ops && r < r_end && ((win >> lane) & 1ull)) {
             // runs: s amplicon residues (Y), the window (M), the rest of the amplicon (Y)
             int q = 0;
@@ -1413,11 +1431,13 @@ __global__ __launch_bounds__(kSegThreads) void nw_band_segsort(const KernelArgs 
     extern __shared__ int seg_sm[];
     // keys: lengths 0 .. cap, cap + 1 (too long for the band), EX = cap + 2 (exact copy, no DP),
     // then the seeded reads' diagonal keys
-    const int NB = a.band_lb_cap + 3 + a.seed_keys, EX = a.band_lb_cap + 2;
+    // ... and the wide-first reads' length keys
+    const int NB = a.band_lb_cap + 3 + a.seed_keys + a.wf_keys, EX = a.band_lb_cap + 2;
     int* cnt = seg_sm;                  // [kSegWaves][NB]: per-wave counts, then prefix over waves
     int* kbase = seg_sm + kSegWaves * NB;   // [NB]: bucket totals, then their exclusive prefix
     int* misc = kbase + NB;             // [0], [4] look-back results (band list, seeded list), [2] error, [16..31] wave sums
-    const int KS = a.seed_list ? a.band_lb_cap + 3 : NB;   // keys >= KS: seeded reads (their own list)
+    const int KW = a.wf_list ? a.band_lb_cap + 3 + a.seed_keys : NB;   // keys >= KW: wide-first reads (their own list)
+    const int KS = a.seed_list ? a.band_lb_cap + 3 : KW;   // keys in [KS, KW): seeded reads (their own list)
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     for (int k = tid; k < kSegWaves * NB + NB; k += kSegThreads) seg_sm[k] = 0;
     if (tid < 32) misc[tid] = 0;
@@ -1485,21 +1505,27 @@ __global__ __launch_bounds__(kSegThreads) void nw_band_segsort(const KernelArgs 
     // their place in the seeded list
     // the seeded list: an odd segment count gets its last entry twice (a pair of one read: the walks take
     // its first position), so every pair of that list lies within one segment's sorted run
-    const int dpB = KS < NB ? kbase[KS] : dp, dpS0 = dp - dpB, dpS = dpS0 + (dpS0 & 1);
+    const int dpK = KW < NB ? kbase[KW] : dp, dpW = dp - dpK;   // (the wide-first list: no padding, the wide band holds any pair)
+    const int dpB = KS < NB ? kbase[KS] : dp, dpS0 = dpK - dpB, dpS = dpS0 + (dpS0 & 1);
     if (wave == 0) {
         const unsigned base = lookback_excl(a.lb_status, blockIdx.x, epoch, (unsigned)dpB, &misc[2]);
         if (lane == 0) misc[0] = (int)base;
     } else if (wave == 1 && a.seed_list) {   // the seeded list: the look-back words after the band list's
         const unsigned base = lookback_excl(a.lb_status + gridDim.x + 1, blockIdx.x, epoch, (unsigned)dpS, &misc[2]);
         if (lane == 0) misc[4] = (int)base;
+    } else if (wave == 2 && a.wf_list) {   // the wide-first list: the third set of look-back words
+        const unsigned base = lookback_excl(a.lb_status + 2 * (gridDim.x + 1), blockIdx.x, epoch, (unsigned)dpW, &misc[2]);
+        if (lane == 0) misc[5] = (int)base;
     }
     __syncthreads();
-    const long long base = misc[0], baseS = misc[4];
+    const long long base = misc[0], baseS = misc[4], baseW = misc[5];
     int32_t* order = const_cast<int32_t*>(a.band_order);
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const int k = key[i];
-        if (k >= KS) {
+        if (k >= KW) {
+            a.wf_list[baseW + (kbase[k] - dpK) + cnt[wave * NB + k] + rank[i]] = (int32_t)(r0 + i);
+        } else if (k >= KS) {
             const int q = (kbase[k] - dpB) + cnt[wave * NB + k] + rank[i];
             a.seed_list[baseS + q] = (int32_t)(r0 + i);
             if (q == dpS0 - 1 && dpS != dpS0) {   // the segment's odd count padded to a pair
@@ -1512,7 +1538,9 @@ __global__ __launch_bounds__(kSegThreads) void nw_band_segsort(const KernelArgs 
     if (tid == 0) {
         if (misc[2]) a.fallback_count[3] = 1;   // look-back cut off: the call reports an error
         if (blockIdx.x == gridDim.x - 1) {
-            *const_cast<int32_t*>(a.band_count) = (int32_t)(base + dpB);
+            // (the wide-first reads are DP reads of the chunk: counted here, listed apart)
+            *const_cast<int32_t*>(a.band_count) = (int32_t)(base + dpB + baseW + dpW);
+            if (a.wf_list) *a.wf_count = (int32_t)(baseW + dpW);
             if (a.seed_list) *a.seed_count = (int32_t)(baseS + dpS);
         }
     }
@@ -1538,12 +1566,18 @@ __device__ __forceinline__ long long l2_redo_n(const KernelArgs& a) {
     return redo_direct_taken(a) ? 0ll : (long long)*a.band_count;
 }
 __device__ __forceinline__ long long l2_seed0(const KernelArgs& a) { return (l2_redo_n(a) + 1) & ~1ll; }
+// Wide first (KernelArgs::wf_list): the launch with wf_take = 1 reads that list when the chunk takes it
+// (wf_taken), nothing otherwise; a launch over the sorted DP list (a.wf_list set: the first level, the
+// redo compaction) reads band_order[0, *band_count - *wf_count) and, unless that launch took it, the
+// wide-first list after it.
 __device__ __forceinline__ long long band_list_count(const KernelArgs& a) {
+    if (a.wf_take == 1) return wf_taken(a) ? (long long)*a.wf_count : 0ll;
     if (a.band_from_work) return exact_work_count(a) + (a.seed_list ? (long long)*a.seed_count : 0ll);
     if (a.seed_l2 == 1) return l2_seed0(a) + (long long)*a.seed_count;
-    return (long long)*a.band_count;
+    return (long long)*a.band_count - (wf_taken(a) ? (long long)*a.wf_count : 0ll);
 }
 __device__ __forceinline__ long long band_list_read(const KernelArgs& a, long long k, long long nb) {
+    if (a.wf_take == 1) return (long long)a.wf_list[k];
     if (a.band_from_work) {
         if (k < nb) return a.work_list[k];
         const long long nr = redo_direct_taken(a) ? (long long)*a.redo_count : 0ll;
@@ -1553,6 +1587,10 @@ __device__ __forceinline__ long long band_list_read(const KernelArgs& a, long lo
         const long long nr = l2_redo_n(a), s0 = (nr + 1) & ~1ll;
         if (k >= s0) return (long long)a.seed_list[k - s0];
         if (k >= nr) --k;   // the hole: its pair's read A again (the pair holds one read)
+    }
+    if (a.wf_list) {
+        const long long nbo = nb - (long long)*a.wf_count;
+        if (k >= nbo) return (long long)a.wf_list[k - nbo];
     }
     return (long long)a.band_order[k];
 }
@@ -1571,6 +1609,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NW_FILL_WPE
     if (W == kBandDiags && redo_direct_taken(a) && a.seed_l2 != 1) return;
     if (W < kBandDiags && l1_skipped(a)) return;   // first level skipped (KernelArgs::l1_skip)
     if (W >= kBandDiags && a.tail_prio) __builtin_amdgcn_s_setprio(3);
+    // beside a wide-first launch (raised priority, as every wide launch): the same, or its wavefronts wait for that one's
+    if (W < kBandDiags && a.wf_list && a.tail_prio) __builtin_amdgcn_s_setprio(3);
+    if (W > kBandDiags && a.wf_take == 1 && blockIdx.x == 0 && threadIdx.x == 0 && wf_taken(a)) *a.wf_taken_n = *a.wf_count;
     const int La = a.La;
     const int O = a.gap_open, E = a.gap_extend;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wpb = blockDim.x >> 6;
@@ -1633,7 +1674,12 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NW_FILL_WPE
             act = LbA <= a.band_lb_cap && LbB <= a.band_lb_cap && band_geometry2(La, LbA, LbB, &dlo, W);
             // the first level (16 diagonals) leaves a pair with a read classify keyed past the band's lengths
             // -- one that needs more diagonals (a known sequence's variant: nw_band_classify) -- to the next
-            if constexpr (W < kBandDiags) act = act && a.sort_key[ra] <= a.band_lb_cap && a.sort_key[rb] <= a.band_lb_cap;
+            // (a wide-first read on this level -- its list was not taken -- is an ordinary read of its length)
+            if constexpr (W < kBandDiags) {
+                const int kw = a.wf_list ? a.band_lb_cap + 3 + a.seed_keys : 0x7fffffff;
+                const int ka = a.sort_key[ra], kb = a.sort_key[rb];
+                act = act && (ka <= a.band_lb_cap || ka >= kw) && (kb <= a.band_lb_cap || kb >= kw);
+            }
             if constexpr (W >= kBandDiags) {
                 // seeded reads (both of the pair): the band centred on their hits' diagonals
                 if (a.seed_info) {
@@ -2626,6 +2672,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(LN ? NW_WAL
     if (W == kBandDiags && redo_direct_taken(a) && a.seed_l2 != 1) return;
     if (W < kBandDiags && l1_skipped(a)) return;   // first level skipped (KernelArgs::l1_skip)
     if (W >= kBandDiags && a.tail_prio) __builtin_amdgcn_s_setprio(3);
+    // beside a wide-first launch (raised priority, as every wide launch): the same, or its wavefronts wait for that one's
+    if (W < kBandDiags && a.wf_list && a.tail_prio) __builtin_amdgcn_s_setprio(3);
     constexpr int CW = W > 64 ? W / 64 : 1;   // captures (band diagonals) per lane
     const int La = a.La, E = a.gap_extend;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, wpb = blockDim.x >> 6;
@@ -3148,7 +3196,7 @@ hipError_t launch_band_sort(const KernelArgs& a, unsigned epoch, hipStream_t s) 
                            dim3(256), (size_t)(8 * ((a.La + 3) / 4)), s, a);
     }
     const int nseg = (int)std::max<int64_t>(1, (a.n + kSegReads - 1) / kSegReads);
-    hipLaunchKernelGGL(nw_band_segsort, dim3(nseg), dim3(kSegThreads), (size_t)segsort_lds_bytes(a.band_lb_cap + a.seed_keys), s, a,
+    hipLaunchKernelGGL(nw_band_segsort, dim3(nseg), dim3(kSegThreads), (size_t)segsort_lds_bytes(a.band_lb_cap + a.seed_keys + a.wf_keys), s, a,
                        epoch);
     return hipGetLastError();
 }
@@ -3157,7 +3205,7 @@ hipError_t launch_band_sort(const KernelArgs& a, unsigned epoch, hipStream_t s) 
 // compactions (1024-read blocks)
 int64_t band_lookback_words(int64_t n) {
     const int64_t seg = std::max<int64_t>(1, (n + kSegReads - 1) / kSegReads);
-    return std::max<int64_t>(std::max<int64_t>(1, (n + 1023) / 1024) + 1, 2 * seg + 2);   // band list, seeded list
+    return std::max<int64_t>(std::max<int64_t>(1, (n + 1023) / 1024) + 1, 3 * seg + 3);   // band, seeded, wide-first list
 }
 
 hipError_t launch_band(int W, const KernelArgs& a, const LaunchCfg& fill, const LaunchCfg& walk, hipStream_t s,

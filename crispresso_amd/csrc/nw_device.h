@@ -62,7 +62,8 @@ struct KernelArgs {
     int32_t band_maxsub;           // largest substitution score (scaled): the certificate's bound
     const uint32_t* band_tab;      // [17 amplicon codes (EDNAFULL, pad)][6][6 read codes] packed int16x2 score + 2 E
     const uint32_t* rowpos;        // [La] codes each amplicon row scores > 0 against (markup ':')
-    int32_t* sort_key;             // [n] bucket of every read: length, band_lb_cap + 1 (longer), + 2 (exact copy)
+    int32_t* sort_key;             // [n] bucket of every read: length, band_lb_cap + 1 (longer), + 2 (exact copy),
+                                   // then the seeded keys (seed_keys) and the wide-first keys (wf_keys)
     const int32_t* band_count;     // device: entries of band_order to align (sorted reads that need the DP,
                                    // or the previous level's redo count)
     unsigned long long* lb_status; // look-back words of the single-pass scans (band_lookback_words(n))
@@ -148,7 +149,29 @@ struct KernelArgs {
     // the HDR pass's reads that are copies of the reference amplicon); classify flags the reads equal
     // to it (nops kNopsKnown) and the compaction gives them that alignment.  Null: off.
     const uint32_t* known2;
+    // wide first: DP reads the 16-diagonal band cannot certify -- known before any DP
+    // from classify's facts: another length than the amplicon's, or a plain read of its length with
+    // wf-many substitutions or more -- take sort keys of their own (wf_keys of them, by length, past
+    // the seeded keys) and the segment sort lists them apart (wf_list, *wf_count; *band_count counts
+    // them too).  A chunk that keeps its first level and lists 1 .. wf_cap of them aligns that list on
+    // the wide level beside the first level (the launch with wf_take = 1, which writes the count to
+    // *wf_taken_n); any other chunk reads the list as the tail of its sorted DP list.  Null wf_list: off.
+    int32_t* wf_list;
+    int32_t* wf_count;
+    int32_t* wf_taken_n;
+    int32_t wf_keys;
+    int32_t wf_cap;
+    int32_t wf_take;
 };
+
+// The wide-first list is aligned by its own launch (decided on the device, the same by every kernel
+// of the chunk: a.band_count is the sort's count).
+__host__ __device__ inline bool l1_skipped(const KernelArgs& a);
+__host__ __device__ inline bool wf_taken(const KernelArgs& a) {
+    if (!a.wf_list || a.wf_cap <= 0) return false;
+    const int32_t n = *a.wf_count;
+    return n > 0 && n <= a.wf_cap && !l1_skipped(a);
+}
 
 // Boundary value of a leading end gap of k residues (0: free end gaps, or k = 0) and
 // the penalty of a trailing one.
@@ -270,14 +293,14 @@ hipError_t launch_exact(const KernelArgs& a, int grid, int lds_bytes, bool tb_ld
 // this chunk's total, [3] errors (1: staging full, 2: spill area full, from opsctl[1], 4: a
 // look-back cut off); running over the call: [4] exact-kernel reads, [5] second band level
 // reads of two-level chunks, [6] reads that needed the DP, [7] DP reads of chunks run on the
-// second level alone, [8] reads that reached the exact kernel (after the wide level) (OpsCounts:
-// the device counters of the chunk's kernels);
+// second level alone, [8] reads that reached the exact kernel (after the wide level), [9] reads the
+// wide-first launch took (counted in [4] too) (OpsCounts: the device counters of the chunk's kernels);
 // [kOpsCtl], [kOpsCtl + 1]: the running base, read from [kOpsCtl + parity] and written to
 // the other (chunk k: parity k & 1).
 // status: band_lookback_words(n) look-back words; epoch: new per launch.  opsctl: the
 // kernels' flags.  hctl: pinned host copy of ctl[0 .. kOpsCtl) written by the launch (or null).
 constexpr int kOpsBlockReads = 1024;
-constexpr int kOpsCtl = 9;
+constexpr int kOpsCtl = 10;
 constexpr int kOpsCtlAll = kOpsCtl + 2;
 struct OpsCounts {
     const int32_t* fallback;   // [0]: exact-kernel reads of the chunk, [3]: look-back error flag
@@ -290,6 +313,7 @@ struct OpsCounts {
     const int32_t* seeded;     // the seeded reads (to the wide level, or the second level first; null: none)
     const int32_t* seeded_l2;  // of those, the ones the 32-diagonal level left to the wide level (null: it took none)
     const int32_t* seed_pad;   // entries the segment sort added to pair up odd segments (counted in seeded)
+    const int32_t* wide_first; // reads the wide-first launch took (KernelArgs::wf_taken_n; null: off)
 };
 // The call's last chunk: the compaction also writes the chunk's records, run offsets and runs
 // straight into the caller's page-locked buffers (no copies and no host round trip after it).

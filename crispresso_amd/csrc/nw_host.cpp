@@ -89,6 +89,8 @@ struct Scratch {
     DevBuf<int32_t> d_cert_q, d_cert_cnt;   // classify's queues for nw_band_cert (KernelArgs::cert_q)
     DevBuf<unsigned long long> d_lb;   // look-back words of the single-pass scans (sort, redo list, ops)
     DevBuf<uint8_t> d_bregion;         // band regions (per read pair)
+    DevBuf<int32_t> d_wf_list;         // wide first: the segment sort's list of those reads
+    DevBuf<uint8_t> d_wf_region;       // ... and their launch's band regions (it runs beside the first level)
     DevBuf<uint32_t> d_slots, d_spill, d_staging;   // ops output: run slots, spill area, compaction output
     DevBuf<int32_t> d_nops, d_opsctl;
     void release() {
@@ -96,13 +98,14 @@ struct Scratch {
         d_redo_flags.release(); d_order.release(); d_sort_key.release(); d_lb.release();
         d_cert_q.release(); d_cert_cnt.release();
         d_seed.release(); d_seed2.release(); d_seed_list.release(); d_seed_flags.release(); d_seed_list2.release();
-        d_bregion.release(); d_slots.release(); d_spill.release(); d_staging.release(); d_nops.release();
+        d_bregion.release(); d_wf_list.release(); d_wf_region.release(); d_slots.release(); d_spill.release(); d_staging.release(); d_nops.release();
         d_opsctl.release();
     }
 };
 constexpr int kScratchSets = 6;   // 3 per pass of a dual call, 3 otherwise
 constexpr int kComputeStreams = 3;
 constexpr int64_t kWidePairs = 2048;     // read pairs of one chunk's wide level (region capacity)
+constexpr int64_t kWideFirstPairs = 4096;   // read pairs of the wide-first launch (its region; twice this: its cap)
 
 // Test switches (environment, read per call).  Each forces a path the defaults reach only on
 // particular inputs, so the tests can hold every path to the oracle:
@@ -114,6 +117,8 @@ constexpr int64_t kWidePairs = 2048;     // read pairs of one chunk's wide level
 //   CRISPR_NW_WIDE       "0": no 128-diagonal level
 //   CRISPR_NW_DIRECT     reads up to which a chunk's first level hands straight to the wide level
 //   CRISPR_NW_L1SKIP     "0": chunks of >= 65536 reads with few DP reads keep the first level
+//   CRISPR_NW_WIDE_FIRST "0": no wide-first list (reads the 16-diagonal band cannot certify wait for it)
+//   CRISPR_NW_WIDE_FIRST_CAP  reads up to which a chunk's wide-first list runs beside the first level
 //   CRISPR_NW_ADAPT      "0": no adaptive level choice across chunks
 //   CRISPR_NW_CHUNK, CRISPR_NW_OPS_SLOT, CRISPR_NW_SPILL_WORDS, CRISPR_NW_REGION_MB: sizes
 //                        (chunk reads, runs per slot, spill words, band region MB)
@@ -177,6 +182,15 @@ struct nw_ctx {
     nw::LaunchCfg wide_fill{}, wide_walk{};
     int64_t wide_pairs = 0, wide_stride = 0;
     int wide_words = 0, wide_lb_cap = 0;
+    // wide first: the wide level's kernels over the segment sort's wide-first list, on
+    // the second compute stream beside the first level (0 pairs: off); wf_call: this chunk of
+    // ops_call may use it (a one-chunk call: no other chunk's kernels on that stream)
+    nw::LaunchCfg wf_fill{}, wf_walk{};
+    int64_t wf_pairs = 0;
+    int wf_cap = 0;
+    bool wf_call = false, wf_chunk = false;
+    hipEvent_t ev_wf0 = nullptr, ev_wf1 = nullptr;   // the fork after the sort, the join before the exact kernel
+    int64_t call_wide_first = 0;       // reads of the last call the wide-first launches took
     // seeded band of the current call: reads the 16-diagonal band cannot hold
     // (La - Lb >= 16) go to the wide level centred on their 16-mer hits; seed_pairs widens the
     // wide level's region for them, seed_keys their sort keys
@@ -654,6 +668,7 @@ int configure(nw_ctx* c) {
         // one level: fill + walk launch configs, region stride and pairs per pass
         // (the wide level at 8, 2 or 4 wavefronts per fill block measured slower or no faster)
         const int wide_fill_wpb = 1, wide_walk_wpb = 2;
+        int occ_fill = 0, occ_walk = 0;   // blocks per CU of the level configured last
         auto level = [&](int W, nw::LaunchCfg& f, nw::LaunchCfg& w, int64_t& stride, int64_t& pass_pairs,
                          int64_t max_pairs = INT64_MAX) -> int {
             f = nw::LaunchCfg{};
@@ -672,6 +687,8 @@ int configure(nw_ctx* c) {
             if (nw::band_occupancy(W, f.wpb, w.wpb, f.lds_bytes, w.lds_bytes, &fb, &wb) != hipSuccess || fb <= 0 ||
                 wb <= 0)
                 return 0;
+            occ_fill = fb;
+            occ_walk = wb;
             const int ppw = W == 16 ? 8 : (W == 32 ? 4 : 1);   // read pairs per wavefront
             stride = nw::band_region_bytes(La, c->lb_max, W);
             pass_pairs = std::max<int64_t>(ppw, std::min<int64_t>(std::min(pairs, max_pairs), cap_bytes / stride));
@@ -702,6 +719,26 @@ int configure(nw_ctx* c) {
                 HIP_OR_FAIL(c, c->s->d_fallback2.reserve((size_t)std::max<int64_t>(c->n, 1)));
             } else {
                 c->wide_fill.grid = 0;
+            }
+            // wide first: the same kernels on a region of their own, at most wf_cap reads of the chunk
+            c->wf_pairs = 0;
+            c->wf_cap = 0;
+            const char* wfe = std::getenv("CRISPR_NW_WIDE_FIRST");
+            if (use16 && c->wide_fill.grid > 0 && !(wfe && std::atoi(wfe) == 0)) {
+                int64_t cap = 2 * kWideFirstPairs;
+                if (const char* e = std::getenv("CRISPR_NW_WIDE_FIRST_CAP")) cap = std::max(0ll, std::atoll(e));
+                if (cap > 0) {   // the wide level's launch shape (its occupancy: no second query), grids for this list
+                    c->wf_pairs = std::max<int64_t>(1, std::min(std::min(pairs, (cap + 1) / 2), cap_bytes / c->wide_stride));
+                    c->wf_cap = (int)std::min<int64_t>(cap, 2 * c->wf_pairs);
+                    c->wf_fill = c->wide_fill;
+                    c->wf_walk = c->wide_walk;
+                    c->wf_fill.grid = (int)std::max<int64_t>(1, std::min<int64_t>((c->wf_pairs + wide_fill_wpb - 1) / wide_fill_wpb,
+                                                                                 (int64_t)c->num_cus * occ_fill));
+                    c->wf_walk.grid = (int)std::max<int64_t>(1, std::min<int64_t>((2 * c->wf_pairs + wide_walk_wpb - 1) / wide_walk_wpb,
+                                                                                 (int64_t)c->num_cus * occ_walk));
+                    HIP_OR_FAIL(c, c->s->d_wf_region.reserve((size_t)(c->wf_pairs * c->wide_stride)));
+                    HIP_OR_FAIL(c, c->s->d_wf_list.reserve((size_t)std::max<int64_t>(c->n, 1)));
+                }
             }
             HIP_OR_FAIL(c, c->s->d_bregion.reserve((size_t)rbytes));
             HIP_OR_FAIL(c, c->s->d_order.reserve((size_t)std::max<int64_t>(c->n, 1)));
@@ -758,7 +795,9 @@ int nw_create(int device, nw_ctx** out) {
         hipEventCreate(&c->ev0) != hipSuccess || hipEventCreate(&c->ev1) != hipSuccess ||
         hipEventCreate(&c->ev_fill) != hipSuccess || hipEventCreate(&c->ev_walk) != hipSuccess ||
         hipEventCreate(&c->ev_sort) != hipSuccess || hipEventCreate(&c->ev_l2) != hipSuccess ||
-        hipEventCreate(&c->ev_h1) != hipSuccess) {
+        hipEventCreate(&c->ev_h1) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_wf0, hipEventDisableTiming) != hipSuccess ||
+        hipEventCreateWithFlags(&c->ev_wf1, hipEventDisableTiming) != hipSuccess) {
         delete c;
         return NW_E_HIP;
     }
@@ -802,6 +841,8 @@ void nw_destroy(nw_ctx* c) {
         if (c->cstream[k]) (void)hipStreamDestroy(c->cstream[k]);
     if (c->s_out) (void)hipStreamDestroy(c->s_out);
     if (c->ev_fill) (void)hipEventDestroy(c->ev_fill);
+    if (c->ev_wf0) (void)hipEventDestroy(c->ev_wf0);
+    if (c->ev_wf1) (void)hipEventDestroy(c->ev_wf1);
     if (c->ev_h1) (void)hipEventDestroy(c->ev_h1);
     if (c->ev_sort) (void)hipEventDestroy(c->ev_sort);
     if (c->ev_l2) (void)hipEventDestroy(c->ev_l2);
@@ -1021,6 +1062,7 @@ hipError_t launch_work(nw_ctx* c, const nw::KernelArgs& a) {
 // uploaded arrays (outputs, records and fallback queue at the same index).
 // Everything is queued on c->stream; nothing synchronises.
 int launch_range(nw_ctx* c, int64_t base) {
+    c->wf_chunk = false;
     c->tail_prio = true;   // the latency-bound kernels of a chunk's chain at raised issue priority (-1.1 %)
     nw::KernelArgs a{};
     a.reads = c->d_reads.p - c->reads_bias;
@@ -1117,6 +1159,23 @@ int launch_range(nw_ctx* c, int64_t base) {
         }
         a.zero_ctl64 = c->zero_ctl;
         a.zero_ctl64_n = nw::kOpsCtlAll;
+        const bool two = c->diag16_fill.grid > 0 && !c->skip16;
+        // wide first: packed input, ops output (classify has each read's substitution
+        // count), an A C G T amplicon of at most 256 bp, a two-level chunk of a resident pass or a
+        // one-chunk call; its keys must fit the segment sort (11 key bits, LDS)
+        {
+            const int wfk = c->diag_lb_cap + 1, nkeys = c->diag_lb_cap + 3 + a.seed_keys + wfk;
+            c->wf_chunk = two && c->wf_pairs > 0 && c->wf_cap > 0 && a.pk_words && a.ops && (c->phases || c->wf_call) &&
+                          a.La <= 256 && c->cur.amp_acgt && c->cur.amp2 && nkeys <= 2048 &&
+                          4 * 17 * nkeys + 128 <= 64 * 1024;
+            if (c->wf_chunk) {
+                a.wf_keys = wfk;
+                a.wf_cap = c->wf_cap;
+                a.wf_list = c->s->d_wf_list.p;
+                a.wf_count = c->s->d_fallback_count.p + 11;   // written by the sort
+                a.wf_taken_n = c->s->d_fallback_count.p + 10; // zeroed by nw_band_classify
+            }
+        }
         HIP_OR_FAIL(c, nw::launch_band_sort(a, next_epoch(c), c->cs));
         tmark(c, "classify+sort");
         const bool pev = c->phases && c->phase_events;   // phase events (resident passes that ask for them)
@@ -1125,7 +1184,6 @@ int launch_range(nw_ctx* c, int64_t base) {
         // level 1 (16 diagonals) over the sorted reads; what it cannot certify -> redo list
         // -> level 2 (32 diagonals) -> the exact int32 kernel.  Kernels clamp the pair
         // ranges to the device-side counts.
-        const bool two = c->diag16_fill.grid > 0 && !c->skip16;
         a.redo_list = c->s->d_redo.p;
         a.redo_count = c->s->d_fallback_count.p + 2;
         if (two) a.redo_flags = c->s->d_redo_flags.p;   // the first level's walk writes every position's
@@ -1148,6 +1206,31 @@ int launch_range(nw_ctx* c, int64_t base) {
             const char* e = std::getenv("CRISPR_NW_L1SKIP");
             a.l1_skip = two && c->wide_fill.grid > 0 && c->n >= 65536 && !(e && std::atoi(e) == 0) ? direct : 0;
         }
+        // the wide-first list on the wide level's kernels beside the first level: the other compute
+        // stream (a hardware queue of its own) from the sort to the exact kernel.  Its give-ups
+        // join the exact kernel's list, as the later wide launch's.
+        hipStream_t wf_side = c->cs == c->cstream[1] ? c->cstream[0] : c->cstream[1];
+        if (c->wf_chunk) {
+            nw::KernelArgs af = a;
+            af.wf_take = 1;
+            af.redo_flags = nullptr;
+            af.seed_info = nullptr;
+            af.seed_info2 = nullptr;
+            af.seed_list = nullptr;
+            af.band_summ = 0;
+            af.band_region = c->s->d_wf_region.p;
+            af.band_stride = c->wide_stride;
+            af.band_words = c->wide_words;
+            af.band_lb_cap = c->wide_lb_cap;
+            af.band_pair_lo = 0;
+            af.band_pair_hi = c->wf_pairs;
+            af.fallback_list = c->s->d_fallback2.p + base;
+            af.fallback_count = c->s->d_fallback_count.p + 6;   // zeroed by nw_band_classify
+            HIP_OR_FAIL(c, hipEventRecord(c->ev_wf0, c->cs));
+            HIP_OR_FAIL(c, hipStreamWaitEvent(wf_side, c->ev_wf0, 0));
+            HIP_OR_FAIL(c, nw::launch_band(nw::kWideDiags, af, c->wf_fill, c->wf_walk, wf_side, nullptr));
+            HIP_OR_FAIL(c, hipEventRecord(c->ev_wf1, wf_side));
+        }
         for (int lvl = two ? 0 : 1; lvl < 2; ++lvl) {
             nw::KernelArgs al = a;
             al.redo_direct = lvl == 1 ? direct : 0;
@@ -1157,6 +1240,7 @@ int launch_range(nw_ctx* c, int64_t base) {
                 tmark(c, "redo");
                 al.band_order = c->s->d_redo.p;
                 al.band_count = a.redo_count;
+                al.wf_list = nullptr;   // (the redo list holds whichever of those reads the first level had)
             }
             if (lvl == 1 && c->seed_chunk && c->seed_l2) {   // then the seeded list
                 al.seed_l2 = 1;
@@ -1190,6 +1274,7 @@ int launch_range(nw_ctx* c, int64_t base) {
             ac.band_count = a.seed_count;
             ac.redo_flags = c->s->d_seed_flags.p;
             ac.l1_skip = 0;
+            ac.wf_list = nullptr;
             ac.redo_list = c->s->d_seed_list2.p;
             ac.redo_count = c->s->d_fallback_count.p + 8;   // zeroed by nw_band_classify
             HIP_OR_FAIL(c, nw::launch_redo_compact(ac, c->n + c->n / 4096 + 2, next_epoch(c), c->cs, true));
@@ -1207,6 +1292,7 @@ int launch_range(nw_ctx* c, int64_t base) {
             // latency where the exact kernel took ~80 us per chunk; its give-ups -> the exact kernel
             nw::KernelArgs aw = a;
             aw.band_from_work = 1;
+            aw.wf_list = nullptr;
             aw.band_count = a.work_count;
             aw.redo_flags = nullptr;
             aw.band_stride = c->wide_stride;
@@ -1222,6 +1308,10 @@ int launch_range(nw_ctx* c, int64_t base) {
             a.work_count = aw.fallback_count;
             a.redo_direct = 0;
         }
+        // the wide-first launch's give-ups are on the exact kernel's list: the join (nothing between the
+        // first level and here reads what that launch writes -- its reads are on no other list, its region
+        // is its own, the lists it shares with the wide launch above grow by atomics)
+        if (c->wf_chunk) HIP_OR_FAIL(c, hipStreamWaitEvent(c->cs, c->ev_wf1, 0));
         HIP_OR_FAIL(c, launch_work(c, a));
         tmark(c, "exact");
         return NW_OK;
@@ -1290,6 +1380,7 @@ int launch_range_ops(nw_ctx* c, int64_t base, hipEvent_t staging_free = nullptr,
             cnt.seed_pad = c->s->d_fallback_count.p + 9;   // the sort's padding entries (zeroed by classify)
         }
         if (c->seed_chunk && c->seed_l2) cnt.seeded_l2 = c->s->d_fallback_count.p + 8;
+        if (c->wf_chunk) cnt.wide_first = c->s->d_fallback_count.p + 10;
     }
     if (c->n <= 0) cnt.fallback = nullptr;
     nw::OpsKnown kn{};
@@ -1525,10 +1616,10 @@ int64_t nw_batch_fallbacks(nw_ctx* c) {
     (void)hipSetDevice(c->device);
     if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
     if (!c->use_diag) return 0;
-    std::vector<int32_t> v(4);
+    std::vector<int32_t> v(11);
     if (hipMemcpy(v.data(), c->s->d_fallback_count.p, v.size() * sizeof(int32_t), hipMemcpyDeviceToHost) != hipSuccess)
         return -1;
-    int64_t total = v[0];
+    int64_t total = v[0] + v[10];   // (the wide-first launch's reads: the wide level's too)
     // a skipped second level (KernelArgs::redo_direct): its reads went to the exact kernel
     if (c->use_diag && c->diag16_fill.grid > 0 && c->redo_direct > 0 && v[2] <= c->redo_direct) total += v[2];
     return total;
@@ -1944,6 +2035,7 @@ int ops_call(nw_ctx* c, const char* reads, const int64_t* offsets, int64_t n, ui
     auto restore = [&](int code) {
         c->seed_on = false;
         c->seed_chunk = false;
+        c->wf_call = false;
         c->seed_pairs = 0;
         c->split_to = nullptr;
         c->skip16 = false;
@@ -2341,6 +2433,7 @@ int ops_call(nw_ctx* c, const char* reads, const int64_t* offsets, int64_t n, ui
         // C3 5.578 vs 5.570, C1 7.082 vs 7.070 -- the same -- while the kernel-resident pass of the
         // same kernels runs 0.81 -> 0.69 ms; the pooled call's 96 small chunks lost: 16.61 vs 17.15 ms)
         c->lane_call = (!groups || dual) && hi - lo >= 65536;
+        c->wf_call = nchunks == 1 && !groups && !dual;   // (the other compute stream is idle)
         c->pkc = nw::KernelArgs{};
         if (pk && upload && !c->use_diag) {   // the exact kernels read bytes: the chunk's bases -> bytes + exceptions
             const int64_t b0 = offsets[lo], b1 = offsets[hi];
@@ -2467,6 +2560,7 @@ int ops_call(nw_ctx* c, const char* reads, const int64_t* offsets, int64_t n, ui
         c->call_counts[2] = any_diag ? (two ? h[5] + h[7] : h[6]) : 0;
         c->call_counts[3] = h[4];
         c->call_exact = h[8];
+        c->call_wide_first = h[9];
     }
     c->call_done = true;
     // device times: the upload span on s_in, the chunks' compute spans summed
@@ -2813,7 +2907,7 @@ int nw_batch_path_counts(nw_ctx* c, int64_t* counts4) {
         counts4[3] = nw_batch_fallbacks(c);
         return NW_OK;
     }
-    int32_t fb[8] = {0, 0, 0, 0, 0, 0, 0, 0}, need = 0;
+    int32_t fb[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, need = 0;
     HIP_OR_FAIL(c, hipMemcpy(fb, c->s->d_fallback_count.p, sizeof fb, hipMemcpyDeviceToHost));
     need = fb[1];   // the sort's DP count
     const bool two = c->diag16_fill.grid > 0;
@@ -2822,8 +2916,20 @@ int nw_batch_path_counts(nw_ctx* c, int64_t* counts4) {
     // a skipped second level (KernelArgs::redo_direct) sent its reads to the exact kernel
     const bool direct = two && c->redo_direct > 0 && fb[2] <= c->redo_direct;
     counts4[2] = two ? (direct ? 0 : fb[2]) : need;   // second level (32 diagonals)
-    counts4[3] = fb[0] + (direct ? fb[2] : 0);        // the 16 / 32 levels' give-ups (wide level + exact kernel)
+    // the 16 / 32 levels' give-ups and the wide-first launch's reads (wide level + exact kernel)
+    counts4[3] = fb[0] + (direct ? fb[2] : 0) + fb[10];
     return NW_OK;
+}
+
+int64_t nw_batch_wide_first_reads(nw_ctx* c) {
+    if (c && c->call_done) return c->call_wide_first;
+    if (!c || !c->ran) return -1;
+    if (!c->use_diag) return 0;
+    (void)hipSetDevice(c->device);
+    if (hipStreamSynchronize(c->stream) != hipSuccess) return -1;
+    int32_t fb[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+    if (hipMemcpy(fb, c->s->d_fallback_count.p, sizeof fb, hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return fb[10];
 }
 
 int64_t nw_batch_exact_reads(nw_ctx* c) {

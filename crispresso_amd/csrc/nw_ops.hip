@@ -171,7 +171,9 @@ __global__ __launch_bounds__(kOpsThreads) void nw_ops_compact(const int32_t* nop
         const long long pw = nw < pad ? nw : pad;
         nw -= pw;
         n2 -= pad - pw;
-        ctl[4] += fb + nw;
+        const long long wf1 = cnt.wide_first ? (long long)*cnt.wide_first : 0ll;   // the wide level's reads too
+        ctl[4] += fb + nw + wf1;
+        ctl[9] += wf1;
         ctl[8] += cnt.exact ? (long long)*cnt.exact : fb;
         if (cnt.redo && !direct) ctl[5] += *cnt.redo;
         ctl[5] += n2;

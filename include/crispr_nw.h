@@ -219,6 +219,11 @@ int nw_batch_path_counts(nw_ctx* ctx, int64_t* counts4);
  * certify), those the 128-diagonal wide level did not certify either: the reads the exact
  * int32 kernel aligned (synchronises; -1 when nothing ran). */
 int64_t nw_batch_exact_reads(nw_ctx* ctx);
+/* Of the reads in nw_batch_path_counts [3], those the wide level took in the first sweep, beside
+ * the 16-diagonal level: DP reads of another length than the amplicon's, or of its length with more
+ * substitutions than the 16-diagonal band can certify, listed apart by the sort (wide
+ * first; CRISPR_NW_WIDE_FIRST=0 disables it).  Synchronises; -1 when nothing ran. */
+int64_t nw_batch_wide_first_reads(nw_ctx* ctx);
 
 /* Output mode of the upload/run API (NW_OUT_ROWS default).  Takes effect from
  * the next nw_batch_upload. */
