@@ -305,6 +305,28 @@ def test_gpu_trim_long_reads():
 
 
 @pytest.mark.gpu
+def test_gpu_trim_batch_larger_than_the_grid():
+    """The launch is capped at 16 blocks of 4 wavefronts per CU: in a larger batch a wavefront clips a
+    second and a third pair over the LDS bytes its previous pair left behind."""
+    try:
+        import torch
+        cus = int(torch.cuda.get_device_properties(0).multi_processor_count)
+    except Exception:
+        cus = 256
+    n = 2 * (4 * 16 * cus) + 5
+    assert n > 4 * 16 * cus
+    e1, e2, _ = synth600_oracle(DEFAULT)
+    idx = np.random.Generator(np.random.PCG64(17)).integers(0, 600, n)
+    pool = synth600()
+    pairs = [pool[j] for j in idx]
+    for minlen in (0, 40):
+        res = gpu_keeps(pairs, DEFAULT, minlen)
+        assert len(res.keep1) == n and len(res.keep2) == n
+        assert_same(res, minlen_applied(e1[idx], minlen), minlen_applied(e2[idx], minlen),
+                    f"batch of {n} MINLEN {minlen}")
+
+
+@pytest.mark.gpu
 def test_gpu_trim_single_end():
     pairs = synth600()
     k1, _, counts = oracle_clip(tmo.IlluminaClip(FASTA + DEFAULT), pairs, single_end=True)
