@@ -298,11 +298,13 @@ __device__ __forceinline__ void load_read_words(const KernelArgs& a, bool c, lon
     rw[16] = 0u;
 }
 // Its main diagonal against the amplicon's words (LDS): mismatches k, the first, second and last
-// mismatching base (-1: none)
+// mismatching base (-1: none); xf_, xl_ (classify<true, true>; null: not wanted): the read's 2-bit difference
+// from the amplicon at f and at l -- the read's base there is the amplicon's XOR it
 __device__ __forceinline__ void main_diag_mism(const unsigned (&rw)[17], const unsigned* amp2s, int La, int* k_, int* f_,
-                                               int* f2_, int* l_) {
+                                               int* f2_, int* l_, unsigned* xf_ = nullptr, unsigned* xl_ = nullptr) {
     const int nw = (La + 15) >> 4;
     int k = 0, f = -1, f2 = -1, l = -1;
+    unsigned xfw = 0u, xlw = 0u;   // the difference words holding f and l
 #pragma unroll
     for (int t = 0; t < 16; ++t) {
         if (t >= nw) continue;
@@ -312,16 +314,93 @@ __device__ __forceinline__ void main_diag_mism(const unsigned (&rw)[17], const u
         if (m != 0u && f >= 0 && f2 < 0) f2 = 16 * t + (__builtin_ctz(m) >> 1);
         if (m != 0u && f < 0) {
             f = 16 * t + (__builtin_ctz(m) >> 1);
+            xfw = x;
             const unsigned m2 = m & (m - 1u);
             if (m2 != 0u) f2 = 16 * t + (__builtin_ctz(m2) >> 1);
         }
-        if (m != 0u) l = 16 * t + ((31 - __builtin_clz(m)) >> 1);
+        if (m != 0u) {
+            l = 16 * t + ((31 - __builtin_clz(m)) >> 1);
+            xlw = x;
+        }
     }
     *k_ = k;
     *f_ = f;
     *f2_ = f2;
     *l_ = l;
+    if (xf_) *xf_ = (xfw >> (2 * (f & 15))) & 3u;
+    if (xl_) *xl_ = (xlw >> (2 * (l & 15))) & 3u;
 }
+
+// The shifted diagonals of a read that equals the amplicon but at its bases f <= l (classify's one- and
+// two-substitution certificates, lane path): on diagonal +-sh it mismatches exactly where the amplicon
+// mismatches itself at that shift (A_sh[q] = amp[q] != amp[q + sh]), but at the one pair per substituted
+// base p that holds the read's base p -- pair q = p - sh of d = +sh (read q + sh against amplicon q), pair
+// q = p of d = -sh (read q against amplicon q + sh).  So a diagonal's count, and its counts over q >= qa and
+// q <= qb, are the prefix counts C_sh of A_sh (the image's last words, nw_host.cpp cls_image: word q holds
+// C_1, C_2, C_3 [q] in its bytes, constant from q = La - sh on) corrected at those pairs.  Per lane: the
+// words f - 3 .. f + 1 and l - 3 .. l + 1 (clamped to [0, La]) and 16 amplicon bases from f - 3 and l - 3.
+struct Sub12Tab {
+    unsigned cf[5], cl[5];   // prefix-count words f - 3 + j, l - 3 + j
+    unsigned af, al;         // amplicon bases from max(f - 3, 0) / max(l - 3, 0)
+    int of, ol;              // f's / l's place in them (<= 3)
+    unsigned rf, rl, tot;    // the read's bases f and l; the totals (word La)
+    int La, f, l;
+    __device__ __forceinline__ void load(const unsigned* selfc, const unsigned* amp2s, int La_, int f_, int l_, unsigned xf,
+                                         unsigned xl) {
+        La = La_;
+        f = f_;
+        l = l_;
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+            cf[j] = selfc[min(max(f - 3 + j, 0), La)];
+            cl[j] = selfc[min(max(l - 3 + j, 0), La)];
+        }
+        tot = selfc[La];
+        const int bf = min(max(f - 3, 0), La), bl = min(max(l - 3, 0), La);   // (a lane without a mismatch: f = l = -1)
+        of = max(f, 0) - bf;
+        ol = max(l, 0) - bl;
+        af = amp_word16(amp2s, bf);
+        al = amp_word16(amp2s, bl);
+        rf = ((af >> (2 * of)) & 3u) ^ xf;
+        rl = ((al >> (2 * ol)) & 3u) ^ xl;
+    }
+    // diagonal d = sgn * sh: mismatches, any at q >= qa, any at q <= qb (nw_band_classify's `shifted`); the
+    // callers' ranges: ENDS (d = +1: qa = f, qb = l - 2; d = -1: qa = f + 1, qb = l - 1), else qa = 0, qb = La
+    template <bool ENDS>
+    __device__ __forceinline__ void shifted(int sgn, int sh, int* tot_, bool* ge, bool* le) const {
+        const int qa = !ENDS ? 0 : (sgn > 0 ? f : f + 1), qb = !ENDS ? La : (sgn > 0 ? l - 2 : l - 1);
+        const int bs = 8 * (sh - 1), n = max(0, La - sh);
+        auto cnt = [&](unsigned w) { return (int)((w >> bs) & 0xffu); };
+        // C_sh at qa and at qb + 1, clamped to [0, n]
+        int ca, cb;
+        if (!ENDS) {
+            ca = 0;
+            cb = cnt(tot);
+        } else if (sgn > 0) {
+            ca = cnt(cf[3]);   // qa = f
+            cb = cnt(cl[2]);   // qb + 1 = l - 1
+        } else {
+            ca = cnt(cf[4]);   // qa = f + 1
+            cb = cnt(cl[3]);   // qb + 1 = l
+        }
+        int t = cnt(tot), g = t - ca, e = cb;
+        // the pair holding the read's base p (j = 3 + q - p: the prefix-count words q and q + 1 of p's five)
+        auto fix = [&](int p, const unsigned (&c)[5], unsigned aw, int o, unsigned rp) {
+            const int q = sgn > 0 ? p - sh : p, j = sgn > 0 ? 3 - sh : 3;
+            const bool in = q >= 0 && q < n;
+            const unsigned other = (aw >> (2 * max(o + (sgn > 0 ? -sh : sh), 0))) & 3u;   // amp[q] / amp[q + sh]
+            const int d = in ? (int)(rp != other) - (cnt(c[j + 1]) - cnt(c[j])) : 0;
+            t += d;
+            if (q >= qa) g += d;
+            if (q <= qb) e += d;
+        };
+        fix(f, cf, af, of, rf);
+        if (l != f) fix(l, cl, al, ol, rl);
+        *tot_ = t;
+        *ge = g > 0;
+        *le = e > 0;
+    }
+};
 
 // The three-substitution certificate's per-read checks (i)-(iii) (classify, below; lanes s3: reads of the
 // amplicon's length with three mismatches on the main diagonal, at bases f < f2 < l; the caller checked
@@ -593,7 +672,10 @@ __device__ __forceinline__ void write_read_bytes(const KernelArgs& a, unsigned l
 #ifndef NW_CLASSIFY_WPE
 #define NW_CLASSIFY_WPE 5
 #endif
-template <bool PK>
+// TAB (packed input): the lane path's one- and two-substitution certificates take their shifted diagonals'
+// facts from the amplicon's self-mismatch prefix counts (the image's last words) instead of word passes
+// over the read -- a template parameter: the kernel's code has to fit the instruction cache
+template <bool PK, bool TAB = false>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY_WPE))) void nw_band_classify(const KernelArgs a) {
     extern __shared__ unsigned amp_sh[];   // [nd] folded amplicon dwords (0 at non-ACGT), [nd] raw dwords
     constexpr int kRbw = 66;               // a window read's 16-base words (Lb < La <= 1024) + a zero word
@@ -686,6 +768,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
     const int n2 = (La + 15) / 16 + 2, nseed = a.n_seed;
     unsigned* skey = amp2s + n2;
     uint16_t* spos = (uint16_t*)(skey + nseed);
+    const unsigned* selfc = amp_sh + (a.cls_words - a.sub12_words);   // [La + 1] self-mismatch prefix counts (TAB)
     const bool win_ok = PK && amp_acgt_all && a.ops && a.band_maxsub == 5 * sc5 && a.gap_extend >= 0 && a.amp2 &&
                         a.gap_open > xl && nseed > 0 && La <= 1024;
     // 16 bases of the packed stream from batch position p, and of the amplicon from position p (LDS)
@@ -749,7 +832,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
                 unsigned rw[17];
                 load_read_words(a, c, my_off, rw);
                 int k, f, f2, l;   // mismatches of the main diagonal, first, second and last base
-                main_diag_mism(rw, amp2s, La, &k, &f, &f2, &l);
+                unsigned xor_f = 0u, xor_l = 0u;   // (TAB) the read's 2-bit difference from the amplicon at f and at l
+                if constexpr (TAB) main_diag_mism(rw, amp2s, La, &k, &f, &f2, &l, &xor_f, &xor_l);
+                else main_diag_mism(rw, amp2s, La, &k, &f, &f2, &l);
                 exact = __ballot(c && k == 0);
                 wf_sub = __ballot(c && wf_k > 0 && k >= wf_k);
                 const bool s1 = c && sub1_ok && k == 1, s2 = c && sub2_ok && k == 2;
@@ -778,8 +863,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
                     // each, d = +1 one at q >= f and one at q <= l - 2, d = -1 at q >= f + 1 and q <= l - 1
                     int tp, tm;
                     bool gp, lp, gm, lm;
-                    shifted(1, 1, f, l - 2, &tp, &gp, &lp);
-                    shifted(-1, 1, f + 1, l - 1, &tm, &gm, &lm);
+                    Sub12Tab tb;
+                    if constexpr (TAB) {
+                        tb.load(selfc, amp2s, La, f, l, xor_f, xor_l);
+                        tb.shifted<true>(1, 1, &tp, &gp, &lp);
+                        tb.shifted<true>(-1, 1, &tm, &gm, &lm);
+                    } else {
+                        shifted(1, 1, f, l - 2, &tp, &gp, &lp);
+                        shifted(-1, 1, f + 1, l - 1, &tm, &gm, &lm);
+                    }
                     sub1 = __ballot(s1 && tp >= 1 && tm >= 1);
                     bool ok2 = s2 && tp >= 2 && tm >= 2 && gp && lp && gm && lm;
                     if (__ballot(ok2)) {   // d = +-2, +-3: one mismatch each
@@ -787,8 +879,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
                         for (int sh = 2; sh <= 3; ++sh) {
                             int t2, t3;
                             bool x0, x1;
-                            shifted(1, sh, 0, La, &t2, &x0, &x1);
-                            shifted(-1, sh, 0, La, &t3, &x0, &x1);
+                            if constexpr (TAB) {
+                                tb.shifted<false>(1, sh, &t2, &x0, &x1);
+                                tb.shifted<false>(-1, sh, &t3, &x0, &x1);
+                            } else {
+                                shifted(1, sh, 0, La, &t2, &x0, &x1);
+                                shifted(-1, sh, 0, La, &t3, &x0, &x1);
+                            }
                             ok2 = ok2 && t2 >= 1 && t3 >= 1;
                         }
                     }
@@ -3184,8 +3281,13 @@ hipError_t launch_band_sort(const KernelArgs& a, unsigned epoch, hipStream_t s) 
     if (a.pk_words) {   // one block per call block of 256 reads the chunk touches
         const int64_t g0 = a.pk_call_lo / 256, g1 = (a.pk_call_lo + a.n - 1) / 256;
         const size_t lds = (size_t)(8 * ((a.La + 3) / 4)) +
-                           (a.amp2 ? (size_t)(4 * ((a.La + 15) / 16 + 2) + 6 * a.n_seed + 16) : 0);
-        hipLaunchKernelGGL(nw_band_classify<true>, dim3((unsigned)(g1 - g0 + 1)), dim3(256), lds, s, a);
+                           (a.amp2 ? (size_t)(4 * ((a.La + 15) / 16 + 2) + 6 * a.n_seed + 16) : 0) +
+                           (size_t)(4 * a.sub12_words);
+        // (the table form: where the lane path runs -- ops output, the image holds the tables)
+        if (a.sub12_table && a.sub12_words > 0 && a.ops && a.amp2 && a.amp_acgt)
+            hipLaunchKernelGGL((nw_band_classify<true, true>), dim3((unsigned)(g1 - g0 + 1)), dim3(256), lds, s, a);
+        else
+            hipLaunchKernelGGL((nw_band_classify<true, false>), dim3((unsigned)(g1 - g0 + 1)), dim3(256), lds, s, a);
         if (a.cert_q) {   // its four wavefronts' queues per block
             const int nslots = (int)(4 * (g1 - g0 + 1));
             hipLaunchKernelGGL(nw_band_cert, dim3((unsigned)((nslots + kCertSlots - 1) / kCertSlots)), dim3(256),

@@ -143,6 +143,10 @@ struct KernelArgs {
     int32_t* cert_cnt;
     const uint32_t* cls_img;       // classify's LDS image of the amplicon (nw_host.cpp cls_image)
     int32_t cls_words;
+    // the image's last words: the amplicon's self-mismatch prefix counts at shifts 1 .. 3 (0: none);
+    // sub12_table: the packed classify takes its one- and two-substitution certificates' shifted
+    // diagonals from them (0: from word passes over the read)
+    int32_t sub12_words, sub12_table;
     int32_t amp_acgt;              // every amplicon byte A C G T (either case)
     // known copies: the 2-bit words of a sequence of the amplicon's length whose
     // alignment against the amplicon is computed once (the previous amplicon of a resident batch:

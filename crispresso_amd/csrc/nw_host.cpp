@@ -67,6 +67,7 @@ struct Profile {
     // classify's LDS image of the amplicon (cls_image): copied as it is by every block
     const uint32_t* cls_img = nullptr;
     int32_t cls_words = 0;
+    int32_t sub12_words = 0;           // the image's self-mismatch prefix counts (its last words; 0: none)
     bool amp_acgt = false;             // every amplicon byte A C G T (either case)
 };
 
@@ -114,6 +115,7 @@ struct Switches {
     bool wide = true;                  // CRISPR_NW_WIDE "0": no 128-diagonal level
     bool wide_first = true;            // CRISPR_NW_WIDE_FIRST "0": no wide-first list (its reads wait for the wide level)
     int64_t wide_first_cap = 2 * kWideFirstPairs;   // CRISPR_NW_WIDE_FIRST_CAP: reads of a chunk's list run beside the first level
+    bool sub12_table = true;           // CRISPR_NW_SUB12_TABLE "0": classify's one- / two-substitution checks by word passes
     int direct = -1;                   // CRISPR_NW_DIRECT: reads up to which the first level hands straight to the wide level
     bool l1skip = true;                // CRISPR_NW_L1SKIP "0": chunks of >= 65536 reads with few DP reads keep the first level
     bool adapt = true;                 // CRISPR_NW_ADAPT "0": no adaptive level choice across chunks
@@ -143,6 +145,7 @@ static Switches read_switches() {
     w.wide = !off("CRISPR_NW_WIDE");
     w.wide_first = !off("CRISPR_NW_WIDE_FIRST");
     if (const char* e = std::getenv("CRISPR_NW_WIDE_FIRST_CAP")) w.wide_first_cap = std::max(0ll, std::atoll(e));
+    w.sub12_table = !off("CRISPR_NW_SUB12_TABLE");
     if (const char* e = std::getenv("CRISPR_NW_DIRECT")) w.direct = std::max(0, std::atoi(e));
     w.l1skip = !off("CRISPR_NW_L1SKIP");
     if (const char* e = std::getenv("CRISPR_NW_ADAPT")) w.adapt = std::strcmp(e, "0") != 0;
@@ -392,6 +395,7 @@ struct AmpTables {
     std::vector<uint32_t> amp2, seed_key;   // window seeds (Profile::amp2 / seed_key / seed_pos)
     std::vector<uint16_t> seed_pos;
     std::vector<uint32_t> cls;              // classify's LDS image (cls_image)
+    int32_t sub12_words = 0;                // its self-mismatch prefix counts (its last words; 0: none)
     bool amp_acgt = false;
 };
 
@@ -399,6 +403,11 @@ struct AmpTables {
 // amplicon (lower-case A C G T, 0 at any other byte and past La), [nd] of its raw bytes (0
 // past La), then, with window seeds, amp2, the seed keys and the seed positions (uint16, two
 // per word) -- one coalesced copy per block instead of per-byte folding and three table loads.
+// Last, for an A C G T amplicon of at most 256 bp, the prefix counts of its self-mismatch at
+// shifts 1, 2, 3 (sub12_words = La + 1 words): with A_sh[q] = amp[q] != amp[q + sh] for q < La - sh
+// (0 from there on), word q holds C_sh[q] = sum of A_sh[i], i < q, in byte sh - 1; word La the
+// totals.  Classify's one- and two-substitution certificates read their shifted diagonals' facts
+// from them.
 void cls_image(const std::string& ref, AmpTables* t) {
     const int La = (int)ref.size(), nd = (La + 3) / 4;
     t->cls.assign((size_t)(2 * nd), 0u);
@@ -410,11 +419,21 @@ void cls_image(const std::string& ref, AmpTables* t) {
         t->cls[(size_t)(q / 4)] |= (uint32_t)(acgt ? (u | 0x20) : 0) << (8 * (q % 4));
         t->cls[(size_t)(nd + q / 4)] |= (uint32_t)c << (8 * (q % 4));
     }
+    t->sub12_words = 0;
     if (t->amp2.empty()) return;
     t->cls.insert(t->cls.end(), t->amp2.begin(), t->amp2.end());
     t->cls.insert(t->cls.end(), t->seed_key.begin(), t->seed_key.end());
     for (size_t i = 0; i < t->seed_pos.size(); i += 2)
         t->cls.push_back((uint32_t)t->seed_pos[i] | (i + 1 < t->seed_pos.size() ? (uint32_t)t->seed_pos[i + 1] << 16 : 0u));
+    // the self-mismatch prefix counts (the lane path's amplicons: A C G T, La <= 256)
+    if (!t->amp_acgt || La > 256) return;
+    uint32_t c[3] = {0u, 0u, 0u};
+    for (int q = 0; q <= La; ++q) {
+        t->cls.push_back(c[0] | c[1] << 8 | c[2] << 16);
+        for (int sh = 1; sh <= 3; ++sh)
+            if (q + sh < La) c[sh - 1] += (ref[(size_t)q] & 0xDF) != (ref[(size_t)(q + sh)] & 0xDF);
+    }
+    t->sub12_words = La + 1;
 }
 
 // The amplicon's 2-bit stream (A C T G = 0 1 2 3 = (byte >> 1) & 3, base p in bits 2 (p % 16)
@@ -579,6 +598,7 @@ int upload_profiles(nw_ctx* c, const std::vector<std::string>& refs, std::vector
         p.R = tabs[g].R;
         p.cls_img = (const uint32_t*)(b + o.cls);
         p.cls_words = (int32_t)tabs[g].cls.size();
+        p.sub12_words = tabs[g].sub12_words;
         p.amp_acgt = tabs[g].amp_acgt;
         if (!tabs[g].amp2.empty()) {
             p.amp2 = (const uint32_t*)(b + o.amp2);
@@ -1149,6 +1169,8 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
         a.n_seed = c->cur.n_seed;
         a.cls_img = c->cur.cls_img;
         a.cls_words = c->cur.cls_words;
+        a.sub12_words = c->cur.sub12_words;
+        a.sub12_table = p.sw->sub12_table ? 1 : 0;
         a.amp_acgt = c->cur.amp_acgt ? 1 : 0;
         // seeded band: the packed classify marks the reads, the segment sort lists them apart
         // (sorted by their hits' diagonals), the wide level takes that list after its own
