@@ -57,6 +57,12 @@ QUANT_EXPORTS = (
 )
 
 
+# Every symbol include/crispr_alleles.h declares.
+ALLELE_EXPORTS = (
+    "nwa_create", "nwa_destroy", "nwa_last_error", "nwa_group_device", "nwa_last_collided", "nwa_phase_times",
+    "nwa_reads_per_step", "nwa_group_host", "nwa_reads_have_lower",
+)
+
 # Every symbol include/crispr_flash.h declares.
 FLASH_EXPORTS = ("nwf_merge_batch", "nwf_last_error")
 
@@ -213,6 +219,17 @@ def load() -> ctypes.CDLL:
         "nwq_lane_fallbacks": (c_int64, [ctx_p]),
         "nwq_run_device_ops": (c_int, [ctx_p, c_char_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                        c_int64, c_int64, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_float)]),
+        "nwa_create": (c_int, [c_int, POINTER(c_void_p)]),
+        "nwa_destroy": (None, [ctx_p]),
+        "nwa_last_error": (c_char_p, [ctx_p]),
+        "nwa_group_device": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
+                                     c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_float)]),
+        "nwa_last_collided": (c_int64, [ctx_p]),
+        "nwa_phase_times": (c_int, [ctx_p, c_void_p]),
+        "nwa_reads_per_step": (c_int64, [ctx_p]),
+        "nwa_group_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
+                                   c_void_p, POINTER(c_int64), c_int32]),
+        "nwa_reads_have_lower": (c_int, [c_void_p, c_void_p, c_int64, c_int32]),
         "nw_synth_offsets": (c_int64, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,
                                         c_int32]),
         "nw_synth_reads": (c_int, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,
@@ -255,7 +272,7 @@ def exported_symbols() -> dict:
     """Map of each declared symbol to whether the loaded library exports it."""
     lib = load()
     out = {}
-    for name in EXPORTS + QUANT_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + SYNTH_EXPORTS:
+    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + SYNTH_EXPORTS:
         try:
             getattr(lib, name)
             out[name] = name not in _MISSING
