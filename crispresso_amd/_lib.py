@@ -67,7 +67,7 @@ ALLELE_EXPORTS = (
 FLASH_EXPORTS = ("nwf_merge_batch", "nwf_last_error")
 
 # Every symbol include/crispr_trim.h declares.
-TRIM_EXPORTS = ("nwt_trim_batch", "nwt_last_error")
+TRIM_EXPORTS = ("nwt_trim_batch", "nwt_trim_program", "nwt_last_error")
 
 # Every symbol include/crispr_synth.h declares (bench / test input generator).
 SYNTH_EXPORTS = ("nw_synth_offsets", "nw_synth_reads")
@@ -84,6 +84,11 @@ class NwtParams(ctypes.Structure):
     """nwt_params (include/crispr_trim.h)."""
     _fields_ = [("seed_mismatches", c_int32), ("palindrome_threshold", c_int32), ("simple_threshold", c_int32),
                 ("min_prefix", c_int32), ("keep_both", c_int32), ("minlen", c_int32)]
+
+
+class NwtStep(ctypes.Structure):
+    """nwt_step (include/crispr_trim.h)."""
+    _fields_ = [("op", c_int32), ("arg", c_int32), ("r", c_float), ("R", c_float)]
 
 
 class NwqParams(ctypes.Structure):
@@ -206,6 +211,9 @@ def load() -> ctypes.CDLL:
         "nwt_trim_batch": (c_int, [c_int, POINTER(NwtParams), c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
                                    c_void_p, c_int32] + [c_void_p] * 6 + [c_int64, c_void_p, c_void_p,
                                                                           POINTER(c_float)]),
+        "nwt_trim_program": (c_int, [c_int, POINTER(NwtParams), c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                     c_void_p, c_int32, POINTER(NwtStep), c_int32] + [c_void_p] * 6
+                             + [c_int64] + [c_void_p] * 4 + [POINTER(c_float)]),
         "nwt_last_error": (c_char_p, []),
         "nwq_create": (c_int, [c_int, POINTER(c_void_p)]),
         "nwq_destroy": (None, [ctx_p]),

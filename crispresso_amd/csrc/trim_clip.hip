@@ -22,6 +22,10 @@
 //     does not matter, and an offset at or past the keep length found so far is skipped.
 // The fp32 sums are formed in the restatement's order (no reassociation, no fma: the
 // terms are only added).  Integer / LDS work, tens of bytes per pair: VALU / LDS bound.
+//
+// The host side of both entries is below the kernel: nwt_trim_batch (this kernel alone) and
+// nwt_trim_program (this kernel, then the steps kernel of trim_steps.hip on the same buffers)
+// share the table building, the validation, the upload and the launch.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,11 +35,10 @@
 #include <string>
 #include <vector>
 
-#include "../../include/crispr_trim.h"
+#include "trim_device.h"
 
 namespace nwt {
 
-constexpr int kWpb = 4;
 constexpr int kMaxPacks = 32;   // adapter 16-mers at 0, 4, 8, ...: (128 - 15 + 3) / 4 = 29
 constexpr int kPrefixQual = 100;
 
@@ -321,18 +324,19 @@ __global__ __launch_bounds__(64 * kWpb) void nwt_clip_kernel(const Args a) {
 
 thread_local std::string g_err;
 
-int fail(int code, const std::string& msg) {
-    g_err = msg;
+// `who` is the entry's name: every message starts with it
+int fail(const char* who, int code, const std::string& msg) {
+    g_err = std::string(who) + ": " + msg;
     return code;
 }
 
 // offsets from 0, ascending, every read <= NWT_MAX_READ; the longest read's length in *lmax
-int check_offsets(const int64_t* off, int64_t n, int* lmax) {
-    if (off[0] != 0) return fail(-1, "nwt_trim_batch: offsets must start at 0");
+int check_offsets(const char* who, const int64_t* off, int64_t n, int* lmax) {
+    if (off[0] != 0) return fail(who, -1, "offsets must start at 0");
     for (int64_t i = 0; i < n; ++i) {
         const int64_t l = off[i + 1] - off[i];
-        if (l < 0) return fail(-1, "nwt_trim_batch: offsets not ascending");
-        if (l > NWT_MAX_READ) return fail(-3, "nwt_trim_batch: reads longer than 4096 bases are not supported");
+        if (l < 0) return fail(who, -1, "offsets not ascending");
+        if (l > NWT_MAX_READ) return fail(who, -3, "reads longer than 4096 bases are not supported");
         *lmax = (int)std::max<int64_t>(*lmax, l);
     }
     return 0;
@@ -342,6 +346,171 @@ bool quals_ok(const uint8_t* q, int64_t n) {
     unsigned bad = 0;
     for (int64_t i = 0; i < n; ++i) bad |= (unsigned)(q[i] < 33) | (unsigned)(q[i] > 126);
     return bad == 0;
+}
+
+// The reads of a batch (n > 0): offsets and quality bytes; the longest read in *lmax.
+int check_reads(const char* who, const uint8_t* qual1, const int64_t* off1, const uint8_t* qual2, const int64_t* off2,
+                int64_t n, bool paired, int* lmax) {
+    int rc = check_offsets(who, off1, n, lmax);
+    if (rc == 0 && paired) rc = check_offsets(who, off2, n, lmax);
+    if (rc != 0) return rc;
+    if (!quals_ok(qual1, off1[n]) || (paired && !quals_ok(qual2, off2[n])))
+        return fail(who, -1, "a quality byte outside 33..126 (phred 33)");
+    return 0;
+}
+
+int check_counts(const char* who, const uint8_t* adapters, const int32_t* adapter_off, const int32_t* adapter_role,
+                 int32_t n_adapters, const uint8_t* prefixes, const int32_t* prefix_off, int32_t n_prefix_pairs) {
+    if (n_adapters < 0 || n_prefix_pairs < 0 || (n_adapters > 0 && (!adapters || !adapter_off || !adapter_role)) ||
+        (n_prefix_pairs > 0 && (!prefixes || !prefix_off)))
+        return fail(who, -1, "null argument or negative count");
+    return 0;
+}
+
+// ILLUMINACLIP's parameters, adapters and prefix pairs into the kernel's tables; the longest
+// prefix in *plmax.
+int build_tables(const char* who, const nwt_params* params, const uint8_t* adapters, const int32_t* adapter_off,
+                 const int32_t* adapter_role, int32_t n_adapters, const uint8_t* prefixes, const int32_t* prefix_off,
+                 int32_t n_prefix_pairs, Tables& T, int* plmax) {
+    if (params->seed_mismatches < 0 || params->palindrome_threshold < 0 || params->simple_threshold < 0 ||
+        params->min_prefix < 0 || params->minlen < 0)
+        return fail(who, -1, "negative parameter");
+    if (n_adapters > NWT_MAX_ADAPTERS) return fail(who, -3, "more than 16 adapters are not supported");
+    if (n_prefix_pairs > NWT_MAX_PREFIX_PAIRS) return fail(who, -3, "more than 4 prefix pairs are not supported");
+    memset(&T, 0, sizeof(T));
+    T.n_adapters = n_adapters;
+    T.n_pp = n_prefix_pairs;
+    if (n_adapters > 0 && adapter_off[0] != 0) return fail(who, -1, "adapter offsets must start at 0");
+    for (int k = 0; k < n_adapters; ++k) {
+        const int len = adapter_off[k + 1] - adapter_off[k];
+        if (len < 0) return fail(who, -1, "adapter offsets not ascending");
+        if (adapter_role[k] < 0 || adapter_role[k] > 2) return fail(who, -1, "adapter role must be 0, 1 or 2");
+        if (len > NWT_MAX_ADAPTER) return fail(who, -3, "adapters longer than 128 bases are not supported");
+        if (len < NWT_MIN_SIMPLE_ADAPTER)
+            return fail(who, -3, "simple-mode adapters shorter than 24 bases (Trimmomatic's short and "
+                                 "medium clipping classes) are not supported");
+        const uint8_t* s = adapters + adapter_off[k];
+        T.alen[k] = len;
+        T.arole[k] = adapter_role[k];
+        T.ank[k] = (len - 15 + 3) / 4;
+        memcpy(T.aseq[k], s, len);
+        for (int j = 0; j < T.ank[k]; ++j) {
+            uint64_t w = 0;
+            for (int t = 0; t < 16; ++t) w = (w << 4) | nib(s[4 * j + t]);
+            T.apack[k][j] = w;
+        }
+    }
+    *plmax = 0;
+    if (n_prefix_pairs > 0 && prefix_off[0] != 0) return fail(who, -1, "prefix offsets must start at 0");
+    for (int k = 0; k < n_prefix_pairs; ++k) {
+        const int l1 = prefix_off[2 * k + 1] - prefix_off[2 * k], l2 = prefix_off[2 * k + 2] - prefix_off[2 * k + 1];
+        if (l1 < 0 || l2 < 0) return fail(who, -1, "prefix offsets not ascending");
+        if (l1 > NWT_MAX_ADAPTER || l2 > NWT_MAX_ADAPTER)
+            return fail(who, -3, "prefixes longer than 128 bases are not supported");
+        const int m = std::min(l1, l2);   // both cut to the shorter one's length from their 3' ends
+        T.plen[k] = m;
+        memcpy(T.p1[k], prefixes + prefix_off[2 * k] + (l1 - m), m);
+        memcpy(T.p2[k], prefixes + prefix_off[2 * k + 1] + (l2 - m), m);
+        *plmax = std::max(*plmax, m);
+    }
+    for (int q = 0; q < 128; ++q) T.mism[q] = (float)(-(double)q / 10.0);
+    return 0;
+}
+
+// The device side of one call: the uploaded reads, the output arrays, two events.  Everything
+// is released when it goes out of scope.
+struct Batch {
+    std::vector<void*> bufs;
+    uint8_t *s1 = nullptr, *q1 = nullptr, *s2 = nullptr, *q2 = nullptr;
+    int64_t *o1 = nullptr, *o2 = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    int cus = 256;
+
+    ~Batch() {
+        if (e0) (void)hipEventDestroy(e0);
+        if (e1) (void)hipEventDestroy(e1);
+        for (void* p : bufs) (void)hipFree(p);
+    }
+    void* dev(size_t bytes) {
+        void* p = nullptr;
+        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
+        bufs.push_back(p);
+        return p;
+    }
+    // allocates the read buffers (the caller allocates its own before upload() and checks them all there)
+    bool alloc_reads(int64_t t1, int64_t t2, int64_t n) {
+        s1 = (uint8_t*)dev(t1 + 8);
+        q1 = (uint8_t*)dev(t1 + 8);
+        s2 = (uint8_t*)dev(t2 + 8);
+        q2 = (uint8_t*)dev(t2 + 8);
+        o1 = (int64_t*)dev(sizeof(int64_t) * (n + 1));
+        o2 = (int64_t*)dev(sizeof(int64_t) * (n + 1));
+        return s1 && q1 && s2 && q2 && o1 && o2;
+    }
+    bool upload(int device, const uint8_t* seq1, const uint8_t* qual1, const int64_t* off1, const uint8_t* seq2,
+                const uint8_t* qual2, const int64_t* off2, int64_t n, bool paired) {
+        const int64_t t1 = off1[n], t2 = paired ? off2[n] : 0;
+        bool ok = hipMemcpy(s1, seq1, t1, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(q1, qual1, t1, hipMemcpyHostToDevice) == hipSuccess &&
+                  hipMemcpy(o1, off1, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess;
+        if (ok && paired)
+            ok = hipMemcpy(s2, seq2, t2, hipMemcpyHostToDevice) == hipSuccess &&
+                 hipMemcpy(q2, qual2, t2, hipMemcpyHostToDevice) == hipSuccess &&
+                 hipMemcpy(o2, off2, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess;
+        ok = ok && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+        hipDeviceProp_t prop;
+        if (ok && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
+            cus = prop.multiProcessorCount;
+        return ok;
+    }
+    // blocks for `items` wavefront jobs at wpb a block: the launch cap both kernels share
+    unsigned grid(int64_t items, int wpb) const {
+        return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + wpb - 1) / wpb, (int64_t)cus * 16));
+    }
+    // what ran between record(e0) and here, in ms
+    bool elapsed(float* ms) {
+        return hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess &&
+               hipEventSynchronize(e1) == hipSuccess && (!ms || hipEventElapsedTime(ms, e0, e1) == hipSuccess);
+    }
+};
+
+// The clip kernel on an uploaded batch; keeps to d_k1 / d_k2.
+bool run_clip(Batch& b, const nwt_params* params, const Tables* d_t, int lmax, int plmax, int64_t n, bool paired,
+              int32_t* d_k1, int32_t* d_k2, float* ms) {
+    Args a{};
+    a.lb = (lmax + plmax + 16 + 15) & ~15;
+    a.lw = a.lb / 8 + 4;
+    const size_t lds_wave = (size_t)8 * a.lb + (size_t)8 * a.lw;
+    // 1 wave: reads in the thousands of bases (<= 38 KB a wave, under 64 KB with the tables)
+    a.wpb = sizeof(Tables) + lds_wave * kWpb <= 65536 ? kWpb : 1;
+    const size_t lds = sizeof(Tables) + lds_wave * a.wpb;
+    a.seq1 = b.s1;
+    a.qual1 = b.q1;
+    a.off1 = b.o1;
+    a.seq2 = b.s2;
+    a.qual2 = b.q2;
+    a.off2 = b.o2;
+    a.n = n;
+    a.keep1 = d_k1;
+    a.keep2 = d_k2;
+    a.t = d_t;
+    a.seed_max = 2 * params->seed_mismatches;
+    const float log10_4 = 0.60206f;
+    a.min_ov = std::min(15, (int)((double)params->simple_threshold / (double)log10_4));
+    a.min_prefix = params->min_prefix;
+    a.keep_both = params->keep_both != 0;
+    a.minlen = params->minlen;
+    a.paired = paired;
+    a.pal_thr = (float)params->palindrome_threshold;
+    a.simple_thr = (float)params->simple_threshold;
+    a.log10_4 = log10_4;
+    if (hipEventRecord(b.e0, nullptr) != hipSuccess) return false;
+    hipLaunchKernelGGL(nwt_clip_kernel, dim3(b.grid(n, a.wpb)), dim3(64 * a.wpb), lds, nullptr, a);
+    return b.elapsed(ms);
+}
+
+int hip_failure(const char* who) {
+    return fail(who, -4, std::string("HIP error: ") + hipGetErrorString(hipGetLastError()));
 }
 
 }  // namespace nwt
@@ -355,149 +524,119 @@ extern "C" int nwt_trim_batch(int device, const nwt_params* params, const uint8_
                               const uint8_t* qual2, const int64_t* off2, int64_t n, int32_t* keep1, int32_t* keep2,
                               float* kernel_ms) {
     using namespace nwt;
+    const char* who = "nwt_trim_batch";
     const bool paired = seq2 != nullptr;
-    if (!params || n < 0 || n_adapters < 0 || n_prefix_pairs < 0 || (n_adapters > 0 && (!adapters || !adapter_off || !adapter_role)) ||
-        (n_prefix_pairs > 0 && (!prefixes || !prefix_off)))
-        return fail(-1, "nwt_trim_batch: null argument or negative count");
+    if (!params || n < 0) return fail(who, -1, "null argument or negative count");
+    int rc = check_counts(who, adapters, adapter_off, adapter_role, n_adapters, prefixes, prefix_off, n_prefix_pairs);
+    if (rc != 0) return rc;
     if (n > 0 && (!seq1 || !qual1 || !off1 || !keep1 || (paired && (!qual2 || !off2 || !keep2))))
-        return fail(-1, "nwt_trim_batch: null argument");
-    if (params->seed_mismatches < 0 || params->palindrome_threshold < 0 || params->simple_threshold < 0 ||
-        params->min_prefix < 0 || params->minlen < 0)
-        return fail(-1, "nwt_trim_batch: negative parameter");
-    if (n_adapters > NWT_MAX_ADAPTERS) return fail(-3, "nwt_trim_batch: more than 16 adapters are not supported");
-    if (n_prefix_pairs > NWT_MAX_PREFIX_PAIRS)
-        return fail(-3, "nwt_trim_batch: more than 4 prefix pairs are not supported");
+        return fail(who, -1, "null argument");
     std::vector<Tables> tv(1);
-    Tables& T = tv[0];
-    memset(&T, 0, sizeof(T));
-    T.n_adapters = n_adapters;
-    T.n_pp = n_prefix_pairs;
-    if (n_adapters > 0 && adapter_off[0] != 0) return fail(-1, "nwt_trim_batch: adapter offsets must start at 0");
-    for (int k = 0; k < n_adapters; ++k) {
-        const int len = adapter_off[k + 1] - adapter_off[k];
-        if (len < 0) return fail(-1, "nwt_trim_batch: adapter offsets not ascending");
-        if (adapter_role[k] < 0 || adapter_role[k] > 2) return fail(-1, "nwt_trim_batch: adapter role must be 0, 1 or 2");
-        if (len > NWT_MAX_ADAPTER) return fail(-3, "nwt_trim_batch: adapters longer than 128 bases are not supported");
-        if (len < NWT_MIN_SIMPLE_ADAPTER)
-            return fail(-3, "nwt_trim_batch: simple-mode adapters shorter than 24 bases (Trimmomatic's short and "
-                            "medium clipping classes) are not supported");
-        const uint8_t* s = adapters + adapter_off[k];
-        T.alen[k] = len;
-        T.arole[k] = adapter_role[k];
-        T.ank[k] = (len - 15 + 3) / 4;
-        memcpy(T.aseq[k], s, len);
-        for (int j = 0; j < T.ank[k]; ++j) {
-            uint64_t w = 0;
-            for (int t = 0; t < 16; ++t) w = (w << 4) | nib(s[4 * j + t]);
-            T.apack[k][j] = w;
-        }
-    }
     int plmax = 0;
-    if (n_prefix_pairs > 0 && prefix_off[0] != 0) return fail(-1, "nwt_trim_batch: prefix offsets must start at 0");
-    for (int k = 0; k < n_prefix_pairs; ++k) {
-        const int l1 = prefix_off[2 * k + 1] - prefix_off[2 * k], l2 = prefix_off[2 * k + 2] - prefix_off[2 * k + 1];
-        if (l1 < 0 || l2 < 0) return fail(-1, "nwt_trim_batch: prefix offsets not ascending");
-        if (l1 > NWT_MAX_ADAPTER || l2 > NWT_MAX_ADAPTER)
-            return fail(-3, "nwt_trim_batch: prefixes longer than 128 bases are not supported");
-        const int m = std::min(l1, l2);   // both cut to the shorter one's length from their 3' ends
-        T.plen[k] = m;
-        memcpy(T.p1[k], prefixes + prefix_off[2 * k] + (l1 - m), m);
-        memcpy(T.p2[k], prefixes + prefix_off[2 * k + 1] + (l2 - m), m);
-        plmax = std::max(plmax, m);
-    }
-    for (int q = 0; q < 128; ++q) T.mism[q] = (float)(-(double)q / 10.0);
+    rc = build_tables(who, params, adapters, adapter_off, adapter_role, n_adapters, prefixes, prefix_off,
+                      n_prefix_pairs, tv[0], &plmax);
+    if (rc != 0) return rc;
     if (kernel_ms) *kernel_ms = 0.0f;
     if (n == 0) return 0;
     int lmax = 0;
-    int rc = check_offsets(off1, n, &lmax);
-    if (rc == 0 && paired) rc = check_offsets(off2, n, &lmax);
+    rc = check_reads(who, qual1, off1, qual2, off2, n, paired, &lmax);
     if (rc != 0) return rc;
-    const int64_t t1 = off1[n], t2 = paired ? off2[n] : 0;
-    if (!quals_ok(qual1, t1) || (paired && !quals_ok(qual2, t2)))
-        return fail(-1, "nwt_trim_batch: a quality byte outside 33..126 (phred 33)");
 
-    Args a{};
-    a.lb = (lmax + plmax + 16 + 15) & ~15;
-    a.lw = a.lb / 8 + 4;
-    const size_t lds_wave = (size_t)8 * a.lb + (size_t)8 * a.lw;
-    // 1 wave: reads in the thousands of bases (<= 38 KB a wave, under 64 KB with the tables)
-    a.wpb = sizeof(Tables) + lds_wave * kWpb <= 65536 ? kWpb : 1;
-    const size_t lds = sizeof(Tables) + lds_wave * a.wpb;
+    if (hipSetDevice(device) != hipSuccess) return fail(who, -4, "hipSetDevice failed");
+    Batch b;
+    const bool have = b.alloc_reads(off1[n], paired ? off2[n] : 0, n);
+    int32_t* d_k1 = (int32_t*)b.dev(sizeof(int32_t) * n);
+    int32_t* d_k2 = (int32_t*)b.dev(sizeof(int32_t) * n);
+    Tables* d_t = (Tables*)b.dev(sizeof(Tables));
+    if (!have || !d_k1 || !d_k2 || !d_t) return fail(who, -4, "hipMalloc failed");
+    bool ok = hipMemcpy(d_t, &tv[0], sizeof(Tables), hipMemcpyHostToDevice) == hipSuccess &&
+              b.upload(device, seq1, qual1, off1, seq2, qual2, off2, n, paired) &&
+              run_clip(b, params, d_t, lmax, plmax, n, paired, d_k1, d_k2, kernel_ms);
+    ok = ok && hipMemcpy(keep1, d_k1, sizeof(int32_t) * n, hipMemcpyDeviceToHost) == hipSuccess &&
+         (!paired || hipMemcpy(keep2, d_k2, sizeof(int32_t) * n, hipMemcpyDeviceToHost) == hipSuccess);
+    if (!ok) return hip_failure(who);
+    return 0;
+}
 
-    if (hipSetDevice(device) != hipSuccess) return fail(-4, "nwt_trim_batch: hipSetDevice failed");
-    std::vector<void*> bufs;
-    auto dev = [&](size_t bytes) -> void* {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return p;
-    };
-    auto cleanup = [&]() {
-        for (void* p : bufs) (void)hipFree(p);
-    };
-    uint8_t* d_s1 = (uint8_t*)dev(t1 + 8);
-    uint8_t* d_q1 = (uint8_t*)dev(t1 + 8);
-    uint8_t* d_s2 = (uint8_t*)dev(t2 + 8);
-    uint8_t* d_q2 = (uint8_t*)dev(t2 + 8);
-    int64_t* d_o1 = (int64_t*)dev(sizeof(int64_t) * (n + 1));
-    int64_t* d_o2 = (int64_t*)dev(sizeof(int64_t) * (n + 1));
-    int32_t* d_k1 = (int32_t*)dev(sizeof(int32_t) * n);
-    int32_t* d_k2 = (int32_t*)dev(sizeof(int32_t) * n);
-    Tables* d_t = (Tables*)dev(sizeof(Tables));
-    if (!d_s1 || !d_q1 || !d_s2 || !d_q2 || !d_o1 || !d_o2 || !d_k1 || !d_k2 || !d_t) {
-        cleanup();
-        return fail(-4, "nwt_trim_batch: hipMalloc failed");
+extern "C" int nwt_trim_program(int device, const nwt_params* clip, const uint8_t* adapters,
+                                const int32_t* adapter_off, const int32_t* adapter_role, int32_t n_adapters,
+                                const uint8_t* prefixes, const int32_t* prefix_off, int32_t n_prefix_pairs,
+                                const nwt_step* steps, int32_t n_steps, const uint8_t* seq1, const uint8_t* qual1,
+                                const int64_t* off1, const uint8_t* seq2, const uint8_t* qual2, const int64_t* off2,
+                                int64_t n, int32_t* start1, int32_t* keep1, int32_t* start2, int32_t* keep2,
+                                float* kernel_ms) {
+    using namespace nwt;
+    const char* who = "nwt_trim_program";
+    const bool paired = seq2 != nullptr;
+    if (n < 0 || n_steps < 0 || (n_steps > 0 && !steps)) return fail(who, -1, "null argument or negative count");
+    int rc = 0;
+    if (clip) {
+        rc = check_counts(who, adapters, adapter_off, adapter_role, n_adapters, prefixes, prefix_off, n_prefix_pairs);
+        if (rc != 0) return rc;
     }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    bool ok = hipMemcpy(d_s1, seq1, t1, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_q1, qual1, t1, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_o1, off1, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_t, &T, sizeof(Tables), hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && paired)
-        ok = hipMemcpy(d_s2, seq2, t2, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(d_q2, qual2, t2, hipMemcpyHostToDevice) == hipSuccess &&
-             hipMemcpy(d_o2, off2, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+    if (n > 0 && (!seq1 || !qual1 || !off1 || !start1 || !keep1 || (paired && (!qual2 || !off2 || !start2 || !keep2))))
+        return fail(who, -1, "null argument");
+    if (n_steps > NWT_MAX_STEPS) return fail(who, -1, "more than 16 steps are not supported");
+    StepsArgs sa{};
+    for (int k = 0; k < n_steps; ++k) {
+        const nwt_step& st = steps[k];
+        if (st.op < NWT_OP_LEADING || st.op > NWT_OP_MINLEN) return fail(who, -1, "unknown step op");
+        if (st.arg < 0 || st.arg > NWT_MAX_STEP_ARG) return fail(who, -1, "a step argument outside 0..2^20");
+        const bool qual = st.op == NWT_OP_LEADING || st.op == NWT_OP_TRAILING || st.op == NWT_OP_AVGQUAL;
+        if (qual && st.arg > NWT_MAX_STEP_QUAL) return fail(who, -1, "a quality threshold above 1000");
+        if (st.op == NWT_OP_SLIDINGWINDOW &&
+            (st.arg < 1 || !(st.r >= 0.0f) || !(st.r <= 3.0e38f) || !(st.R >= 0.0f) || !(st.R <= 3.0e38f)))
+            return fail(who, -1, "SLIDINGWINDOW needs a window of at least 1 and a finite quality >= 0");
+        sa.steps[k] = st;
+    }
+    sa.n_steps = n_steps;
+    std::vector<Tables> tv(1);
+    int plmax = 0;
+    if (clip) {
+        if (clip->minlen != 0) return fail(who, -1, "the clip parameters' minlen must be 0 (MINLEN is a step)");
+        rc = build_tables(who, clip, adapters, adapter_off, adapter_role, n_adapters, prefixes, prefix_off,
+                          n_prefix_pairs, tv[0], &plmax);
+        if (rc != 0) return rc;
+    }
+    if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0f;
+    if (n == 0) return 0;
+    int lmax = 0;
+    rc = check_reads(who, qual1, off1, qual2, off2, n, paired, &lmax);
+    if (rc != 0) return rc;
+
+    if (hipSetDevice(device) != hipSuccess) return fail(who, -4, "hipSetDevice failed");
+    Batch b;
+    const bool have = b.alloc_reads(off1[n], paired ? off2[n] : 0, n);
+    int32_t* d_out[4];   // start1, keep1, start2, keep2
+    bool have_out = true;
+    for (int k = 0; k < 4; ++k) have_out = (d_out[k] = (int32_t*)b.dev(sizeof(int32_t) * n)) != nullptr && have_out;
+    int32_t* d_c1 = clip ? (int32_t*)b.dev(sizeof(int32_t) * n) : nullptr;
+    int32_t* d_c2 = clip ? (int32_t*)b.dev(sizeof(int32_t) * n) : nullptr;
+    Tables* d_t = clip ? (Tables*)b.dev(sizeof(Tables)) : nullptr;
+    if (!have || !have_out || (clip && (!d_c1 || !d_c2 || !d_t))) return fail(who, -4, "hipMalloc failed");
+    bool ok = b.upload(device, seq1, qual1, off1, seq2, qual2, off2, n, paired);
+    if (ok && clip)
+        ok = hipMemcpy(d_t, &tv[0], sizeof(Tables), hipMemcpyHostToDevice) == hipSuccess &&
+             run_clip(b, clip, d_t, lmax, plmax, n, paired, d_c1, d_c2, kernel_ms ? kernel_ms + 0 : nullptr);
     if (ok) {
-        a.seq1 = d_s1;
-        a.qual1 = d_q1;
-        a.off1 = d_o1;
-        a.seq2 = d_s2;
-        a.qual2 = d_q2;
-        a.off2 = d_o2;
-        a.n = n;
-        a.keep1 = d_k1;
-        a.keep2 = d_k2;
-        a.t = d_t;
-        a.seed_max = 2 * params->seed_mismatches;
-        const float log10_4 = 0.60206f;
-        a.min_ov = std::min(15, (int)((double)params->simple_threshold / (double)log10_4));
-        a.min_prefix = params->min_prefix;
-        a.keep_both = params->keep_both != 0;
-        a.minlen = params->minlen;
-        a.paired = paired;
-        a.pal_thr = (float)params->palindrome_threshold;
-        a.simple_thr = (float)params->simple_threshold;
-        a.log10_4 = log10_4;
-        int dev_cus = 256;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-            dev_cus = prop.multiProcessorCount;
-        const int64_t grid =
-            std::max<int64_t>(1, std::min<int64_t>((n + a.wpb - 1) / a.wpb, (int64_t)dev_cus * 16));
-        ok = hipEventRecord(e0, nullptr) == hipSuccess;
+        sa.seq[0] = b.s1, sa.qual[0] = b.q1, sa.off[0] = b.o1;
+        sa.seq[1] = b.s2, sa.qual[1] = b.q2, sa.off[1] = b.o2;
+        sa.keep_in[0] = d_c1, sa.keep_in[1] = paired ? d_c2 : nullptr;
+        sa.start[0] = d_out[0], sa.keep[0] = d_out[1], sa.start[1] = d_out[2], sa.keep[1] = d_out[3];
+        sa.n = n;
+        sa.paired = paired;
+        const size_t lds_wave = steps_lds_per_wave(lmax, &sa.lb);
+        // 1 wave: reads in the thousands of bases (<= 21 KB a wave)
+        sa.wpb = lds_wave * kWpb <= 65536 ? kWpb : 1;
+        ok = hipEventRecord(b.e0, nullptr) == hipSuccess;
         if (ok) {
-            hipLaunchKernelGGL(nwt_clip_kernel, dim3((unsigned)grid), dim3(64 * a.wpb), lds, nullptr, a);
-            ok = hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess &&
-                 hipEventSynchronize(e1) == hipSuccess;
+            launch_steps(sa, b.grid(paired ? 2 * n : n, sa.wpb), lds_wave * sa.wpb);
+            ok = b.elapsed(kernel_ms ? kernel_ms + 1 : nullptr);
         }
-        if (ok && kernel_ms) ok = hipEventElapsedTime(kernel_ms, e0, e1) == hipSuccess;
-        ok = ok && hipMemcpy(keep1, d_k1, sizeof(int32_t) * n, hipMemcpyDeviceToHost) == hipSuccess &&
-             (!paired || hipMemcpy(keep2, d_k2, sizeof(int32_t) * n, hipMemcpyDeviceToHost) == hipSuccess);
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    cleanup();
-    if (!ok) return fail(-4, std::string("nwt_trim_batch: HIP error: ") + hipGetErrorString(hipGetLastError()));
+    int32_t* host[4] = {start1, keep1, start2, keep2};
+    for (int k = 0; ok && k < (paired ? 4 : 2); ++k)
+        ok = hipMemcpy(host[k], d_out[k], sizeof(int32_t) * n, hipMemcpyDeviceToHost) == hipSuccess;
+    if (!ok) return hip_failure(who);
     return 0;
 }

@@ -1,17 +1,20 @@
-/* crispr_trim.h -- C ABI of the MI355X adapter trimming (Trimmomatic 0.33 ILLUMINACLIP + MINLEN).
+/* crispr_trim.h -- C ABI of the MI355X read trimming (Trimmomatic 0.33: ILLUMINACLIP, MINLEN,
+ * and through nwt_trim_program the quality and crop steps).
  *
  * CRISPResso trims paired-end reads with the external Trimmomatic program before the
  * merge when --trim_sequences is given (CRISPResso/CRISPRessoCORE.py:1620-1640):
  *
  *     java -jar trimmomatic-0.33.jar PE -phred33 R1 R2 fp fu rp ru ILLUMINACLIP:<fa>:0:90:10:0:true MINLEN:40
  *
- * This library call clips a batch of read pairs on the GPU with the algorithm the
+ * nwt_trim_batch clips a batch of read pairs on the GPU with the algorithm the
  * test-infrastructure restatement oracle/trimmomatic_oracle.py states (IlluminaClip.process,
  * ClipSeq.compare / quality, maximum_range, PrefixPair.compare / quality, _cut and the
  * MINLEN step of run_pe), float32 sums included.  Clipping only ever truncates a read at
  * its 3' end, so the result is one length per read; no bases are copied.  The binding
  * is crispresso_amd/trim.py (ctypes), whose run_trimmomatic_pe() writes Trimmomatic's
- * four output files.
+ * four output files.  nwt_trim_program runs the same clip and then the other steps of a
+ * --trimmomatic_options_string (nwt_step below) on the same device buffers; its result is
+ * one window (start, length) per read.
  *
  * Only Trimmomatic's "long" clipping class is implemented: a simple-mode adapter of
  * fewer than 24 bases is refused (-3).  The restatement states that class alone (the
@@ -63,7 +66,50 @@ int nwt_trim_batch(int device, const nwt_params* params, const uint8_t* adapters
                    const int64_t* off1, const uint8_t* seq2, const uint8_t* qual2, const int64_t* off2, int64_t n,
                    int32_t* keep1, int32_t* keep2, float* kernel_ms);
 
-/* Message of the last failed nwt_trim_batch call in this thread. */
+/* One step of a Trimmomatic program after the optional ILLUMINACLIP (tests/trim_steps_model.py
+ * restates them).  A record is a window (start, len) of its read, or
+ * dropped; q[i] is the phred-33 quality of base i of the window, 0 where the base is 'N'
+ * (zeroN: LEADING, TRAILING, SLIDINGWINDOW, AVGQUAL).
+ *   LEADING:t        first i with q[i] >= t -> (start + i, len - i); none: dropped
+ *   TRAILING:t       last i >= 1 with q[i] >= t -> (start, i + 1); none: dropped (index 0 is never tested)
+ *   SLIDINGWINDOW:w:r  len < w: dropped; the first window of w bases whose total is below
+ *                    R = float32(r) * float32(w): the first one drops the read, window j >= 1 cuts it to
+ *                    j + w - 1; then bases with (float)q < r are walked back from the end, down to one base
+ *   CROP:n           len >= n -> (start, n)
+ *   HEADCROP:n       len <= n: dropped, else (start + n, len - n)
+ *   AVGQUAL:t        sum(q) < t * len: dropped
+ *   MINLEN:n         len < n: dropped */
+enum { NWT_OP_LEADING = 1, NWT_OP_TRAILING = 2, NWT_OP_SLIDINGWINDOW = 3, NWT_OP_CROP = 4, NWT_OP_HEADCROP = 5,
+       NWT_OP_AVGQUAL = 6, NWT_OP_MINLEN = 7 };
+enum { NWT_MAX_STEPS = 16, NWT_MAX_STEP_ARG = 1 << 20, NWT_MAX_STEP_QUAL = 1000 };
+
+typedef struct nwt_step {
+    int32_t op;  /* NWT_OP_* */
+    int32_t arg; /* t, n, or SLIDINGWINDOW's w (>= 1) */
+    float r;     /* SLIDINGWINDOW's required quality, 0 otherwise */
+    float R;     /* r * w as a float32 product */
+} nwt_step;
+
+/* ILLUMINACLIP (optional) followed by up to NWT_MAX_STEPS steps, on n reads or read pairs.
+ * clip == NULL: no ILLUMINACLIP (the adapter and prefix arguments are unused); otherwise as
+ * nwt_trim_batch, and clip->minlen must be 0 (MINLEN is a step here).  Reads, adapters and
+ * prefixes as nwt_trim_batch; seq2 == NULL: single-end (start2 / keep2 unused).
+ *
+ * One upload; the clip kernel (when clip is given), then the steps kernel on the same device
+ * buffers.  Output: read i survives as seq[start[i] .. start[i] + keep[i]); keep[i] = -1 (and
+ * start[i] = 0): dropped.  A read ILLUMINACLIP clips to nothing is dropped; an empty read enters
+ * the steps as the live (0, 0).  kernel_ms (may be NULL) receives two device times: the clip
+ * kernel's (0 without clip) and the steps kernel's.  Error codes as nwt_trim_batch; more than
+ * NWT_MAX_STEPS steps, an unknown op, an argument above NWT_MAX_STEP_ARG, a quality threshold
+ * above NWT_MAX_STEP_QUAL and SLIDINGWINDOW with w = 0 or a negative or non-finite r are -1. */
+int nwt_trim_program(int device, const nwt_params* clip, const uint8_t* adapters, const int32_t* adapter_off,
+                     const int32_t* adapter_role, int32_t n_adapters, const uint8_t* prefixes,
+                     const int32_t* prefix_off, int32_t n_prefix_pairs, const nwt_step* steps, int32_t n_steps,
+                     const uint8_t* seq1, const uint8_t* qual1, const int64_t* off1, const uint8_t* seq2,
+                     const uint8_t* qual2, const int64_t* off2, int64_t n, int32_t* start1, int32_t* keep1,
+                     int32_t* start2, int32_t* keep2, float* kernel_ms);
+
+/* Message of the last failed nwt_trim_batch / nwt_trim_program call in this thread. */
 const char* nwt_last_error(void);
 
 #ifdef __cplusplus
