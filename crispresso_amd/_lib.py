@@ -69,6 +69,9 @@ FLASH_EXPORTS = ("nwf_merge_batch", "nwf_last_error")
 # Every symbol include/crispr_trim.h declares.
 TRIM_EXPORTS = ("nwt_trim_batch", "nwt_trim_program", "nwt_last_error")
 
+# Every symbol include/crispr_front.h declares.
+FRONT_EXPORTS = ("nwp_prepare", "nwp_fetch", "nwp_release", "nwp_last_error")
+
 # Every symbol include/crispr_synth.h declares (bench / test input generator).
 SYNTH_EXPORTS = ("nw_synth_offsets", "nw_synth_reads")
 NWF_COMBINED, NWF_OUTIE = 1, 2
@@ -89,6 +92,25 @@ class NwtParams(ctypes.Structure):
 class NwtStep(ctypes.Structure):
     """nwt_step (include/crispr_trim.h)."""
     _fields_ = [("op", c_int32), ("arg", c_int32), ("r", c_float), ("R", c_float)]
+
+
+class NwpParams(ctypes.Structure):
+    """nwp_params (include/crispr_front.h)."""
+    _fields_ = [("min_avg_quality", c_int32), ("min_single_quality", c_int32), ("clip", POINTER(NwtParams)),
+                ("adapters", c_void_p), ("adapter_off", c_void_p), ("adapter_role", c_void_p),
+                ("n_adapters", c_int32), ("prefixes", c_void_p), ("prefix_off", c_void_p),
+                ("n_prefix_pairs", c_int32), ("steps", POINTER(NwtStep)), ("n_steps", c_int32),
+                ("flash", NwfParams), ("want_quals", c_int32)]
+
+
+class NwpResult(ctypes.Structure):
+    """nwp_result (include/crispr_front.h)."""
+    _fields_ = [("n", c_int64), ("m", c_int64), ("total", c_int64), ("n_exc", c_int64), ("counts", c_int64 * 5),
+                ("trim", c_int64 * 4), ("kernel_ms", c_float * 5), ("handle", c_void_p)]
+
+
+NWP_FILTERED, NWP_TRIMMED, NWP_NOT_COMBINED, NWP_COMBINED, NWP_COMBINED_OUTIE = range(5)
+NWP_MS = ("filter", "clip", "steps", "merge", "pack")
 
 
 class NwqParams(ctypes.Structure):
@@ -215,6 +237,10 @@ def load() -> ctypes.CDLL:
                                      c_void_p, c_int32, POINTER(NwtStep), c_int32] + [c_void_p] * 6
                              + [c_int64] + [c_void_p] * 4 + [POINTER(c_float)]),
         "nwt_last_error": (c_char_p, []),
+        "nwp_prepare": (c_int, [ctx_p, POINTER(NwpParams)] + [c_void_p] * 6 + [c_int64, POINTER(NwpResult)]),
+        "nwp_fetch": (c_int, [POINTER(NwpResult)] + [c_void_p] * 9),
+        "nwp_release": (None, [POINTER(NwpResult)]),
+        "nwp_last_error": (c_char_p, []),
         "nwq_create": (c_int, [c_int, POINTER(c_void_p)]),
         "nwq_destroy": (None, [ctx_p]),
         "nwq_last_error": (c_char_p, [ctx_p]),
@@ -280,7 +306,7 @@ def exported_symbols() -> dict:
     """Map of each declared symbol to whether the loaded library exports it."""
     lib = load()
     out = {}
-    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + SYNTH_EXPORTS:
+    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + SYNTH_EXPORTS:
         try:
             getattr(lib, name)
             out[name] = name not in _MISSING

@@ -284,6 +284,11 @@ class GpuAligner:
             _lib.ptr(pr.exc_pos) if len(pr.exc_pos) else None, _lib.ptr(pr.exc_byte) if len(pr.exc_byte) else None,
             len(pr.exc_pos)), "nw_batch_upload_packed")
 
+    def adopted(self, buf: Optional[np.ndarray], offsets: np.ndarray) -> None:
+        """The front end (nwp_prepare, ``frontend.prepare_packed``) left a batch in the context as
+        upload_packed would have: record its text and offsets for download_ops / ops_to_dataframe."""
+        self._buf, self._off = buf, offsets
+
     def set_known(self, seq: Optional[str]) -> None:
         """nw_set_known: reads equal to `seq` take one alignment of it (the HDR amplicon during the
         amplicon pass of the dual alignment); None clears it."""

@@ -24,29 +24,11 @@
 #include <string>
 #include <vector>
 
-#include "../../include/crispr_flash.h"
+#include "flash_device.h"
 
 namespace nwf {
 
 constexpr int kMaxLen = 4096;
-constexpr int kWpb = 4;
-
-struct Args {
-    const uint8_t* seq1;
-    const uint8_t* qual1;
-    const int64_t* off1;
-    const uint8_t* seq2;
-    const uint8_t* qual2;
-    const int64_t* off2;
-    int64_t n;
-    uint8_t* out_seq;
-    uint8_t* out_qual;
-    int32_t* out_len;
-    int32_t* out_flags;
-    int32_t min_ov, max_ov, allow_outies, phred, cap;
-    float max_density;
-    int32_t lbuf;   // LDS bytes per staged read (>= longest read, 16-B multiple)
-};
 
 __device__ __forceinline__ uint8_t canon(uint8_t c) {
     const uint8_t u = (c >= 'a' && c <= 'z') ? (uint8_t)(c - 32) : c;
@@ -69,6 +51,10 @@ __device__ __forceinline__ bool better(const Cand& x, const Cand& y) {
     return x.d < y.d || (x.d == y.d && (x.q < y.q || (x.q == y.q && x.o < y.o)));
 }
 
+// WIN: the pair's reads are the windows a.start / a.keep of the uploaded reads and a pair with
+// a.live[p] == 0 or a dropped mate (keep < 0) is written as not combined (the front end,
+// front_pack.hip); without WIN those pointers are never read.
+template <bool WIN>
 __global__ __launch_bounds__(64 * kWpb) void nwf_merge_kernel(const Args a) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -78,14 +64,31 @@ __global__ __launch_bounds__(64 * kWpb) void nwf_merge_kernel(const Args a) {
     unsigned char* q2 = r2 + a.lbuf;                // read 2 qualities, reversed
     for (int64_t p = (int64_t)blockIdx.x * kWpb + wave; p < a.n; p += (int64_t)gridDim.x * kWpb) {
         const int64_t o1 = a.off1[p], o2 = a.off2[p];
-        const int n1 = (int)(a.off1[p + 1] - o1), n2 = (int)(a.off2[p + 1] - o2);
+        int n1 = (int)(a.off1[p + 1] - o1), n2 = (int)(a.off2[p + 1] - o2);
+        int64_t w1 = o1, w2 = o2;   // the first base of each mate
+        if (WIN) {
+            bool live = !a.live || a.live[p] != 0;
+            if (a.keep1) {
+                const int k1 = a.keep1[p], k2 = a.keep2[p];
+                live = live && k1 >= 0 && k2 >= 0;
+                n1 = max(k1, 0), n2 = max(k2, 0);
+                w1 += a.start1[p], w2 += a.start2[p];
+            }
+            if (!live) {   // uniform over the wave
+                if (lane == 0) {
+                    a.out_len[p] = 0;
+                    a.out_flags[p] = 0;
+                }
+                continue;
+            }
+        }
         for (int k = lane; k < n1; k += 64) {
-            r1[k] = canon(a.seq1[o1 + k]);
-            q1[k] = (uint8_t)(a.qual1[o1 + k] - a.phred);
+            r1[k] = canon(a.seq1[w1 + k]);
+            q1[k] = (uint8_t)(a.qual1[w1 + k] - a.phred);
         }
         for (int k = lane; k < n2; k += 64) {
-            r2[n2 - 1 - k] = comp(canon(a.seq2[o2 + k]));
-            q2[n2 - 1 - k] = (uint8_t)(a.qual2[o2 + k] - a.phred);
+            r2[n2 - 1 - k] = comp(canon(a.seq2[w2 + k]));
+            q2[n2 - 1 - k] = (uint8_t)(a.qual2[w2 + k] - a.phred);
         }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
@@ -200,6 +203,23 @@ __global__ __launch_bounds__(64 * kWpb) void nwf_merge_kernel(const Args a) {
     }
 }
 
+void launch_merge(const Args& a, unsigned grid, size_t lds, bool windows) {
+    if (windows)
+        hipLaunchKernelGGL(nwf_merge_kernel<true>, dim3(grid), dim3(64 * kWpb), lds, nullptr, a);
+    else
+        hipLaunchKernelGGL(nwf_merge_kernel<false>, dim3(grid), dim3(64 * kWpb), lds, nullptr, a);
+}
+
+void set_params(Args& a, const nwf_params* params, int lmax) {
+    a.min_ov = params->min_overlap;
+    a.max_ov = params->max_overlap;
+    a.allow_outies = params->allow_outies;
+    a.phred = params->phred_offset;
+    a.cap = params->cap_mismatch_quals;
+    a.max_density = params->max_mismatch_density;
+    a.lbuf = (lmax + 16 + 15) & ~15;
+}
+
 thread_local std::string g_err;
 
 int fail(int code, const std::string& msg) {
@@ -278,14 +298,8 @@ extern "C" int nwf_merge_batch(int device, const nwf_params* params, const uint8
         a.out_qual = d_oq;
         a.out_len = d_len;
         a.out_flags = d_flg;
-        a.min_ov = params->min_overlap;
-        a.max_ov = params->max_overlap;
-        a.allow_outies = params->allow_outies;
-        a.phred = params->phred_offset;
-        a.cap = params->cap_mismatch_quals;
-        a.max_density = params->max_mismatch_density;
-        a.lbuf = (lmax + 16 + 15) & ~15;
-        const size_t lds = (size_t)4 * a.lbuf * kWpb;
+        set_params(a, params, lmax);
+        const size_t lds = merge_lds(a);
         int dev_cus = 256;
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
@@ -293,7 +307,7 @@ extern "C" int nwf_merge_batch(int device, const nwf_params* params, const uint8
         const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n + kWpb - 1) / kWpb, (int64_t)dev_cus * 16));
         ok = hipEventRecord(e0, nullptr) == hipSuccess;
         if (ok) {
-            hipLaunchKernelGGL(nwf_merge_kernel, dim3((unsigned)grid), dim3(64 * kWpb), lds, nullptr, a);
+            launch_merge(a, (unsigned)grid, lds, false);
             ok = hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess &&
                  hipEventSynchronize(e1) == hipSuccess;
         }

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/crispr_nw.h"
+#include "front_device.h"
 #include "host_pool.h"
 #include "nw_device.h"
 #include "nw_edna.h"
@@ -999,10 +1000,24 @@ int nw_batch_upload(nw_ctx* c, const char* reads, const int64_t* offsets, int64_
 
 int nw_batch_upload_packed(nw_ctx* c, const uint8_t* packed, const int64_t* offsets, const uint16_t* lens, int64_t n,
                            const int64_t* exc_pos, const uint8_t* exc_byte, int64_t n_exc) {
+    const nw_front::PackedSrc src{packed, lens, nullptr, exc_pos, exc_byte, false, nullptr};
+    return nw_front::set_packed_batch(c, src, offsets, lens, n, n_exc);
+}
+
+}  // extern "C"
+
+// nw_batch_upload_packed, and nw_front::adopt_packed with the batch already in HBM (src.on_device:
+// the copies are device-to-device, ordered after src.ready on the context's stream).
+int nw_front::set_packed_batch(nw_ctx* c, const PackedSrc& src, const int64_t* offsets, const uint16_t* lens, int64_t n,
+                               int64_t n_exc) {
+    const uint8_t* packed = src.packed;
+    const int64_t* exc_pos = src.exc_pos;
+    const uint8_t* exc_byte = src.exc_byte;
+    const hipMemcpyKind kind = src.on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     if (!c) return NW_E_INVALID;
     if (c->ref.empty()) return fail(c, NW_E_STATE, "nw_set_reference must come first");
     if (c->out_mode != NW_OUT_OPS) return fail(c, NW_E_STATE, "a packed batch needs nw_batch_set_output(NW_OUT_OPS)");
-    if (n <= 0 || !offsets || !packed || !lens || (n_exc > 0 && (!exc_pos || !exc_byte)) || n_exc < 0)
+    if (n <= 0 || !offsets || !packed || !lens || !src.lens || (n_exc > 0 && (!exc_pos || !exc_byte)) || n_exc < 0)
         return fail(c, NW_E_INVALID, "bad batch");
     (void)hipSetDevice(c->device);
     const int La = (int)c->ref.size();
@@ -1033,14 +1048,17 @@ int nw_batch_upload_packed(nw_ctx* c, const uint8_t* packed, const int64_t* offs
     std::vector<int64_t> gb((size_t)ngroups);
     for (int64_t g = 0; g < ngroups; ++g) gb[(size_t)g] = offsets[g * nw::kLenGroup];
     c->resident_ok = false;
-    HIP_OR_FAIL(c, hipMemcpyAsync(c->d_packed.p + (q0 - P0), packed + q0, (size_t)(pk_hi - q0), hipMemcpyHostToDevice,
-                                  c->stream));
+    if (src.ready) HIP_OR_FAIL(c, hipStreamWaitEvent(c->stream, src.ready, 0));
+    HIP_OR_FAIL(c, hipMemcpyAsync(c->d_packed.p + (q0 - P0), packed + q0, (size_t)(pk_hi - q0), kind, c->stream));
     if (n_exc) {
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_exc_pos.p, exc_pos, 8 * (size_t)n_exc, hipMemcpyHostToDevice, c->stream));
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_exc_byte.p, exc_byte, (size_t)n_exc, hipMemcpyHostToDevice, c->stream));
+        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_exc_pos.p, exc_pos, 8 * (size_t)n_exc, kind, c->stream));
+        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_exc_byte.p, exc_byte, (size_t)n_exc, kind, c->stream));
     }
-    HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p, gb.data(), 8 * (size_t)ngroups, hipMemcpyHostToDevice, c->stream));
-    HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p + 8 * ngroups, lens, 2 * (size_t)n, hipMemcpyHostToDevice, c->stream));
+    if (src.on_device)
+        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p, src.gbase, 8 * (size_t)ngroups, kind, c->stream));
+    else
+        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p, gb.data(), 8 * (size_t)ngroups, kind, c->stream));
+    HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p + 8 * ngroups, src.lens, 2 * (size_t)n, kind, c->stream));
     HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
     c->reads_bias = base0 & ~(int64_t)15;
     const Switches sw = read_switches();
@@ -1076,7 +1094,14 @@ int nw_batch_upload_packed(nw_ctx* c, const uint8_t* packed, const int64_t* offs
     return NW_OK;
 }
 
-}  // extern "C"
+int nw_front::check_state(nw_ctx* c) {
+    if (!c) return NW_E_INVALID;
+    if (c->ref.empty()) return fail(c, NW_E_STATE, "nw_set_reference must come first");
+    if (c->out_mode != NW_OUT_OPS) return fail(c, NW_E_STATE, "a packed batch needs nw_batch_set_output(NW_OUT_OPS)");
+    return NW_OK;
+}
+
+int nw_front::device_of(const nw_ctx* c) { return c->device; }
 
 namespace {
 

@@ -52,6 +52,12 @@ struct alignas(16) Tables {
     float mism[128];   // float32(-q / 10.0), the division in double
 };
 
+// Program::tables holds one Tables, aligned within the bytes
+inline Tables* host_tables(Program& P) {
+    const uintptr_t a = (uintptr_t)P.tables.data();
+    return (Tables*)((a + alignof(Tables) - 1) & ~(uintptr_t)(alignof(Tables) - 1));
+}
+
 struct Args {
     const uint8_t* seq1;
     const uint8_t* qual1;
@@ -417,63 +423,6 @@ int build_tables(const char* who, const nwt_params* params, const uint8_t* adapt
     return 0;
 }
 
-// The device side of one call: the uploaded reads, the output arrays, two events.  Everything
-// is released when it goes out of scope.
-struct Batch {
-    std::vector<void*> bufs;
-    uint8_t *s1 = nullptr, *q1 = nullptr, *s2 = nullptr, *q2 = nullptr;
-    int64_t *o1 = nullptr, *o2 = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    int cus = 256;
-
-    ~Batch() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        for (void* p : bufs) (void)hipFree(p);
-    }
-    void* dev(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return p;
-    }
-    // allocates the read buffers (the caller allocates its own before upload() and checks them all there)
-    bool alloc_reads(int64_t t1, int64_t t2, int64_t n) {
-        s1 = (uint8_t*)dev(t1 + 8);
-        q1 = (uint8_t*)dev(t1 + 8);
-        s2 = (uint8_t*)dev(t2 + 8);
-        q2 = (uint8_t*)dev(t2 + 8);
-        o1 = (int64_t*)dev(sizeof(int64_t) * (n + 1));
-        o2 = (int64_t*)dev(sizeof(int64_t) * (n + 1));
-        return s1 && q1 && s2 && q2 && o1 && o2;
-    }
-    bool upload(int device, const uint8_t* seq1, const uint8_t* qual1, const int64_t* off1, const uint8_t* seq2,
-                const uint8_t* qual2, const int64_t* off2, int64_t n, bool paired) {
-        const int64_t t1 = off1[n], t2 = paired ? off2[n] : 0;
-        bool ok = hipMemcpy(s1, seq1, t1, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(q1, qual1, t1, hipMemcpyHostToDevice) == hipSuccess &&
-                  hipMemcpy(o1, off1, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess;
-        if (ok && paired)
-            ok = hipMemcpy(s2, seq2, t2, hipMemcpyHostToDevice) == hipSuccess &&
-                 hipMemcpy(q2, qual2, t2, hipMemcpyHostToDevice) == hipSuccess &&
-                 hipMemcpy(o2, off2, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-        hipDeviceProp_t prop;
-        if (ok && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
-        return ok;
-    }
-    // blocks for `items` wavefront jobs at wpb a block: the launch cap both kernels share
-    unsigned grid(int64_t items, int wpb) const {
-        return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + wpb - 1) / wpb, (int64_t)cus * 16));
-    }
-    // what ran between record(e0) and here, in ms
-    bool elapsed(float* ms) {
-        return hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess &&
-               hipEventSynchronize(e1) == hipSuccess && (!ms || hipEventElapsedTime(ms, e0, e1) == hipSuccess);
-    }
-};
-
 // The clip kernel on an uploaded batch; keeps to d_k1 / d_k2.
 bool run_clip(Batch& b, const nwt_params* params, const Tables* d_t, int lmax, int plmax, int64_t n, bool paired,
               int32_t* d_k1, int32_t* d_k2, float* ms) {
@@ -507,6 +456,70 @@ bool run_clip(Batch& b, const nwt_params* params, const Tables* d_t, int lmax, i
     if (hipEventRecord(b.e0, nullptr) != hipSuccess) return false;
     hipLaunchKernelGGL(nwt_clip_kernel, dim3(b.grid(n, a.wpb)), dim3(64 * a.wpb), lds, nullptr, a);
     return b.elapsed(ms);
+}
+
+// nwt_trim_program's checks of its program (after the null checks), the steps by value and
+// ILLUMINACLIP's tables.
+int program_check(const char* who, const nwt_params* clip, const uint8_t* adapters, const int32_t* adapter_off,
+                  const int32_t* adapter_role, int32_t n_adapters, const uint8_t* prefixes, const int32_t* prefix_off,
+                  int32_t n_prefix_pairs, const nwt_step* steps, int32_t n_steps, Program& P) {
+    if (n_steps > NWT_MAX_STEPS) return fail(who, -1, "more than 16 steps are not supported");
+    P.sa = StepsArgs{};
+    for (int k = 0; k < n_steps; ++k) {
+        const nwt_step& st = steps[k];
+        if (st.op < NWT_OP_LEADING || st.op > NWT_OP_MINLEN) return fail(who, -1, "unknown step op");
+        if (st.arg < 0 || st.arg > NWT_MAX_STEP_ARG) return fail(who, -1, "a step argument outside 0..2^20");
+        const bool qual = st.op == NWT_OP_LEADING || st.op == NWT_OP_TRAILING || st.op == NWT_OP_AVGQUAL;
+        if (qual && st.arg > NWT_MAX_STEP_QUAL) return fail(who, -1, "a quality threshold above 1000");
+        if (st.op == NWT_OP_SLIDINGWINDOW &&
+            (st.arg < 1 || !(st.r >= 0.0f) || !(st.r <= 3.0e38f) || !(st.R >= 0.0f) || !(st.R <= 3.0e38f)))
+            return fail(who, -1, "SLIDINGWINDOW needs a window of at least 1 and a finite quality >= 0");
+        P.sa.steps[k] = st;
+    }
+    P.sa.n_steps = n_steps;
+    P.clip = clip != nullptr;
+    P.plmax = 0;
+    if (clip) {
+        if (clip->minlen != 0) return fail(who, -1, "the clip parameters' minlen must be 0 (MINLEN is a step)");
+        P.params = *clip;
+        P.tables.resize(sizeof(Tables) + alignof(Tables));
+        return build_tables(who, clip, adapters, adapter_off, adapter_role, n_adapters, prefixes, prefix_off,
+                            n_prefix_pairs, *host_tables(P), &P.plmax);
+    }
+    return 0;
+}
+
+// The device arrays a program needs beside the reads, owned by b: the windows (d_out: start1,
+// keep1, start2, keep2) and, with a clip, its lengths and tables.
+bool program_alloc(Batch& b, Program& P, int64_t n, int32_t* d_out[4]) {
+    bool have = true;
+    for (int k = 0; k < 4; ++k) have = (d_out[k] = (int32_t*)b.dev(sizeof(int32_t) * n)) != nullptr && have;
+    P.d_c1 = P.clip ? (int32_t*)b.dev(sizeof(int32_t) * n) : nullptr;
+    P.d_c2 = P.clip ? (int32_t*)b.dev(sizeof(int32_t) * n) : nullptr;
+    P.d_t = P.clip ? b.dev(sizeof(Tables)) : nullptr;
+    return have && (!P.clip || (P.d_c1 && P.d_c2 && P.d_t));
+}
+
+// The clip kernel (with a clip), then the steps kernel, on the uploaded batch (null stream).
+bool program_run(Batch& b, Program& P, int lmax, int64_t n, bool paired, int32_t* const d_out[4], float* kernel_ms) {
+    if (P.clip &&
+        !(hipMemcpy(P.d_t, host_tables(P), sizeof(Tables), hipMemcpyHostToDevice) == hipSuccess &&
+          run_clip(b, &P.params, (const Tables*)P.d_t, lmax, P.plmax, n, paired, P.d_c1, P.d_c2,
+                   kernel_ms ? kernel_ms + 0 : nullptr)))
+        return false;
+    StepsArgs& sa = P.sa;
+    sa.seq[0] = b.s1, sa.qual[0] = b.q1, sa.off[0] = b.o1;
+    sa.seq[1] = b.s2, sa.qual[1] = b.q2, sa.off[1] = b.o2;
+    sa.keep_in[0] = P.d_c1, sa.keep_in[1] = paired ? P.d_c2 : nullptr;
+    sa.start[0] = d_out[0], sa.keep[0] = d_out[1], sa.start[1] = d_out[2], sa.keep[1] = d_out[3];
+    sa.n = n;
+    sa.paired = paired;
+    const size_t lds_wave = steps_lds_per_wave(lmax, &sa.lb);
+    // 1 wave: reads in the thousands of bases (<= 21 KB a wave)
+    sa.wpb = lds_wave * kWpb <= 65536 ? kWpb : 1;
+    if (hipEventRecord(b.e0, nullptr) != hipSuccess) return false;
+    launch_steps(sa, b.grid(paired ? 2 * n : n, sa.wpb), lds_wave * sa.wpb);
+    return b.elapsed(kernel_ms ? kernel_ms + 1 : nullptr);
 }
 
 int hip_failure(const char* who) {
@@ -576,28 +589,10 @@ extern "C" int nwt_trim_program(int device, const nwt_params* clip, const uint8_
     }
     if (n > 0 && (!seq1 || !qual1 || !off1 || !start1 || !keep1 || (paired && (!qual2 || !off2 || !start2 || !keep2))))
         return fail(who, -1, "null argument");
-    if (n_steps > NWT_MAX_STEPS) return fail(who, -1, "more than 16 steps are not supported");
-    StepsArgs sa{};
-    for (int k = 0; k < n_steps; ++k) {
-        const nwt_step& st = steps[k];
-        if (st.op < NWT_OP_LEADING || st.op > NWT_OP_MINLEN) return fail(who, -1, "unknown step op");
-        if (st.arg < 0 || st.arg > NWT_MAX_STEP_ARG) return fail(who, -1, "a step argument outside 0..2^20");
-        const bool qual = st.op == NWT_OP_LEADING || st.op == NWT_OP_TRAILING || st.op == NWT_OP_AVGQUAL;
-        if (qual && st.arg > NWT_MAX_STEP_QUAL) return fail(who, -1, "a quality threshold above 1000");
-        if (st.op == NWT_OP_SLIDINGWINDOW &&
-            (st.arg < 1 || !(st.r >= 0.0f) || !(st.r <= 3.0e38f) || !(st.R >= 0.0f) || !(st.R <= 3.0e38f)))
-            return fail(who, -1, "SLIDINGWINDOW needs a window of at least 1 and a finite quality >= 0");
-        sa.steps[k] = st;
-    }
-    sa.n_steps = n_steps;
-    std::vector<Tables> tv(1);
-    int plmax = 0;
-    if (clip) {
-        if (clip->minlen != 0) return fail(who, -1, "the clip parameters' minlen must be 0 (MINLEN is a step)");
-        rc = build_tables(who, clip, adapters, adapter_off, adapter_role, n_adapters, prefixes, prefix_off,
-                          n_prefix_pairs, tv[0], &plmax);
-        if (rc != 0) return rc;
-    }
+    Program P;
+    rc = program_check(who, clip, adapters, adapter_off, adapter_role, n_adapters, prefixes, prefix_off,
+                       n_prefix_pairs, steps, n_steps, P);
+    if (rc != 0) return rc;
     if (kernel_ms) kernel_ms[0] = kernel_ms[1] = 0.0f;
     if (n == 0) return 0;
     int lmax = 0;
@@ -608,32 +603,9 @@ extern "C" int nwt_trim_program(int device, const nwt_params* clip, const uint8_
     Batch b;
     const bool have = b.alloc_reads(off1[n], paired ? off2[n] : 0, n);
     int32_t* d_out[4];   // start1, keep1, start2, keep2
-    bool have_out = true;
-    for (int k = 0; k < 4; ++k) have_out = (d_out[k] = (int32_t*)b.dev(sizeof(int32_t) * n)) != nullptr && have_out;
-    int32_t* d_c1 = clip ? (int32_t*)b.dev(sizeof(int32_t) * n) : nullptr;
-    int32_t* d_c2 = clip ? (int32_t*)b.dev(sizeof(int32_t) * n) : nullptr;
-    Tables* d_t = clip ? (Tables*)b.dev(sizeof(Tables)) : nullptr;
-    if (!have || !have_out || (clip && (!d_c1 || !d_c2 || !d_t))) return fail(who, -4, "hipMalloc failed");
-    bool ok = b.upload(device, seq1, qual1, off1, seq2, qual2, off2, n, paired);
-    if (ok && clip)
-        ok = hipMemcpy(d_t, &tv[0], sizeof(Tables), hipMemcpyHostToDevice) == hipSuccess &&
-             run_clip(b, clip, d_t, lmax, plmax, n, paired, d_c1, d_c2, kernel_ms ? kernel_ms + 0 : nullptr);
-    if (ok) {
-        sa.seq[0] = b.s1, sa.qual[0] = b.q1, sa.off[0] = b.o1;
-        sa.seq[1] = b.s2, sa.qual[1] = b.q2, sa.off[1] = b.o2;
-        sa.keep_in[0] = d_c1, sa.keep_in[1] = paired ? d_c2 : nullptr;
-        sa.start[0] = d_out[0], sa.keep[0] = d_out[1], sa.start[1] = d_out[2], sa.keep[1] = d_out[3];
-        sa.n = n;
-        sa.paired = paired;
-        const size_t lds_wave = steps_lds_per_wave(lmax, &sa.lb);
-        // 1 wave: reads in the thousands of bases (<= 21 KB a wave)
-        sa.wpb = lds_wave * kWpb <= 65536 ? kWpb : 1;
-        ok = hipEventRecord(b.e0, nullptr) == hipSuccess;
-        if (ok) {
-            launch_steps(sa, b.grid(paired ? 2 * n : n, sa.wpb), lds_wave * sa.wpb);
-            ok = b.elapsed(kernel_ms ? kernel_ms + 1 : nullptr);
-        }
-    }
+    if (!program_alloc(b, P, n, d_out) || !have) return fail(who, -4, "hipMalloc failed");
+    bool ok = b.upload(device, seq1, qual1, off1, seq2, qual2, off2, n, paired) &&
+              program_run(b, P, lmax, n, paired, d_out, kernel_ms);
     int32_t* host[4] = {start1, keep1, start2, keep2};
     for (int k = 0; ok && k < (paired ? 4 : 2); ++k)
         ok = hipMemcpy(host[k], d_out[k], sizeof(int32_t) * n, hipMemcpyDeviceToHost) == hipSuccess;
