@@ -298,7 +298,7 @@ __device__ int walk_runs_wide(const Nib& nib, int La, int Lb, int ei, int ej, un
 // score of amplicon row ai against residue code (only its sign matters).
 // Ops output (KernelArgs::ops): the runs (LDS, end -> start order) of read rd, start
 // -> end, into its slot, or -- more runs than a slot holds -- into the spill area
-// (bump-allocated, the position in slot[0]).  A full spill area sets ops_ctl[1]
+// (bump-allocated, the position in slot[0]).  A full spill area sets ops_ctl[kSpillFull]
 // (the host reports it).  Rows are not written in this mode.
 __device__ inline void store_ops(const KernelArgs& a, long long rd, const unsigned* runs, int nruns, int lane) {
     // the walk / exact kernels: one read per wave, its runs contiguous in the row-major area
@@ -313,7 +313,7 @@ __device__ inline void store_ops(const KernelArgs& a, long long rd, const unsign
         pos = __builtin_amdgcn_readfirstlane(pos);
         if ((long long)pos + nruns > a.spill_cap) {
             if (lane == 0) {
-                atomicOr(a.ops_ctl + 1, 1);
+                atomicOr(a.ops_ctl + kSpillFull, 1);
                 a.nops[rd] = 0;
             }
             return;

@@ -49,7 +49,7 @@ struct KernelArgs {
     int32_t work_lo;           // first work-list entry (or read, null list) this kernel takes (the one-wave
                                // kernel after the multi-wave one: entries [0, exact grid) are the multi-wave kernel's)
     const uint8_t* lut6;       // [256] ascii -> A T G C N pad in that order (0..5), 6 = other IUPAC code
-    // certified diagonal-band kernels (nw_band.hip)
+    // certified diagonal-band kernels (nw_band_device.h and the stage files beside it)
     const int32_t* band_order;     // read indices sorted by length; sorted positions 2g, 2g+1 = pair g
     int64_t band_pair_lo, band_pair_hi;   // pairs of this pass
     uint8_t* band_region;          // per-pair regions of the pass (band_stride bytes each)
@@ -94,7 +94,7 @@ struct KernelArgs {
     int32_t* nops;                 // [n] runs per read (0: empty read)
     uint32_t* spill;
     int64_t spill_cap;             // words
-    int32_t* ops_ctl;              // [0] spill words used, [1] error flag (spill area full)
+    int32_t* ops_ctl;              // SpillCtl: spill words used, error flag (spill area full)
     // exact multi-wave kernel (nw_exact.hip): [17 amplicon codes][4] dwords, the scaled
     // EDNAFULL scores against read codes 0..15 as int8 (byte j of dword q: code 4q + j)
     const uint32_t* sub16;
@@ -167,6 +167,65 @@ struct KernelArgs {
     int32_t wf_cap;
     int32_t wf_take;
 };
+
+// The chunk's counters: one int32[kChunkCounters] block per chunk (KernelArgs::fallback_count of the
+// chunk's first launches points at its head); the count pointers of KernelArgs and OpsCounts are its
+// slots.  Zeroed, all of them, by nw_band_classify's block 0 (the band path) or the host's memset.
+constexpr int kChunkCounters = 16;
+enum ChunkCounter : int {
+    kCntExact = 0,      // the 16- / 32-diagonal levels' give-ups (their walks' atomics), or -- no band path -- nw_kernel.hip's own
+                        // give-ups (its atomics): the exact kernels' work list count
+    kCntDp = 1,         // reads that need the DP (band_count): written by nw_band_segsort's last block
+    kCntRedo = 2,       // reads the first level hands on (redo_count): its walk's atomics, then nw_band_redo_compact writes it
+    kCntLookback = 3,   // a look-back was cut off: set by nw_band_segsort / nw_band_redo_compact, read by the ops compaction and the host
+    kCntReserved4 = 4,  // (unused)
+    kCntReserved5 = 5,  // (unused)
+    kCntWideGiveUp = 6, // the wide launches' give-ups, the exact kernel's list after them: their walks' atomics
+    kCntSeeded = 7,     // seeded list entries (seed_count): written by nw_band_segsort's last block
+    kCntSeededL2 = 8,   // of those, left to the wide level by the 32-diagonal level: written by the seeded list's nw_band_redo_compact
+    kCntSeedPad = 9,    // entries the sort added to pair up odd segments: nw_band_segsort's atomics
+    kCntWfTaken = 10,   // reads the wide-first launch took (wf_taken_n): written by its nw_band_fill
+    kCntWfCount = 11,   // wide-first list entries (wf_count): written by nw_band_segsort's last block
+    kCntReservedTail = 12,   // 12 .. 15 (unused)
+    kCntCount = 16
+};
+static_assert(kCntCount == kChunkCounters, "classify zeroes, and the host copies back, kChunkCounters words: every slot");
+static_assert(kCntWfCount < kCntReservedTail, "a named slot in the reserved tail");
+static_assert(kCntExact == 0 && kCntLookback == 3, "the exact list's count heads the block; the host reads the error flag at [3]");
+
+// KernelArgs::ops_ctl, int32[kSpillCtl]: zeroed with the chunk's counters
+enum SpillCtl : int {
+    kSpillUsed = 0,   // spill words used: the bump allocation of the kernels that write runs
+    kSpillFull = 1,   // set by a kernel that found the spill area full; read by the ops compaction
+    kSpillCtl
+};
+
+// The ops compaction's control block (nw_ops.hip), int64[kOpsCtlAll]: zeroed by the host at a call's
+// start or by nw_band_classify (KernelArgs::zero_ctl64), written by the compaction's last block of
+// each chunk, which also copies [0, kOpsCtl) to the host (hctl).  The counts from kCtlExact on run
+// over the call (OpsCounts: the chunk's counters).
+enum OpsCtl : int {
+    kCtlTotal = 0,        // running total of runs after this chunk
+    kCtlBase = 1,         // this chunk's base in the call's run array
+    kCtlChunkTotal = 2,   // this chunk's runs
+    kCtlError = 3,        // OpsError bits (any block's atomicOr, the last block's from the counters)
+    kCtlExact = 4,        // reads past the 16- / 32-diagonal levels (the wide-first launch's too)
+    kCtlL2 = 5,           // second band level reads of two-level chunks
+    kCtlDp = 6,           // reads that needed the DP
+    kCtlDpOneLevel = 7,   // DP reads of chunks run on the second level alone
+    kCtlReachedExact = 8, // reads that reached the exact kernel (after the wide level)
+    kCtlWideFirst = 9,    // reads the wide-first launch took (counted in kCtlExact too)
+    kOpsCtl               // [kOpsCtl], [kOpsCtl + 1]: the running base, read from [kOpsCtl + parity] and
+                          // written to the other (chunk k: parity k & 1)
+};
+constexpr int kOpsCtlAll = kOpsCtl + 2;
+enum OpsError : int {
+    kOpsErrStaging = 1,    // the staging array is full
+    kOpsErrSpill = 2,      // a kernel found the spill area full (kSpillFull)
+    kOpsErrLookback = 4    // a look-back was cut off (kCntLookback, or the compaction's own)
+};
+static_assert(kOpsCtl == kCtlWideFirst + 1 && kOpsCtl == 10, "the host's pinned copies hold kOpsCtl words per chunk");
+static_assert(kCtlTotal == 0 && kCtlError == 3, "the call's total heads the block; its error word is [3]");
 
 // The wide-first list is aligned by its own launch (decided on the device, the same by every kernel
 // of the chunk: a.band_count is the sort's count).
@@ -243,7 +302,7 @@ __host__ __device__ inline int seed2_n0(int32_t s) { return (int)((unsigned)s & 
 __host__ __device__ inline int seed2_cmax(int32_t s) { return (int)(((unsigned)s >> 7) & 0x7fu); }
 __host__ __device__ inline int seed2_shift(int32_t s) { return (int)(((unsigned)s >> 14) & 0xffffu); }
 
-// certified diagonal-band fill + walk (nw_band.hip): kBandDiags diagonals per read,
+// certified diagonal-band fill + walk (nw_band_fill.hip, nw_band_walk.hip): kBandDiags diagonals per read,
 // two equal-length reads per 16-lane row, reads sorted by length on the device.
 constexpr int kBandDiags = 32;
 constexpr int kWideDiags = 128;   // the wide level: the narrower levels' give-ups before the exact kernel
@@ -293,25 +352,16 @@ hipError_t launch_exact(const KernelArgs& a, int grid, int lds_bytes, bool tb_ld
                         hipStream_t s);
 
 // ops compaction (nw_ops.hip): per-read slots -> one contiguous run array, one launch.
-// ctl (int64, kOpsCtl + 2): [0] running total after this chunk, [1] this chunk's base, [2]
-// this chunk's total, [3] errors (1: staging full, 2: spill area full, from opsctl[1], 4: a
-// look-back cut off); running over the call: [4] exact-kernel reads, [5] second band level
-// reads of two-level chunks, [6] reads that needed the DP, [7] DP reads of chunks run on the
-// second level alone, [8] reads that reached the exact kernel (after the wide level), [9] reads the
-// wide-first launch took (counted in [4] too) (OpsCounts: the device counters of the chunk's kernels);
-// [kOpsCtl], [kOpsCtl + 1]: the running base, read from [kOpsCtl + parity] and written to
-// the other (chunk k: parity k & 1).
-// status: band_lookback_words(n) look-back words; epoch: new per launch.  opsctl: the
-// kernels' flags.  hctl: pinned host copy of ctl[0 .. kOpsCtl) written by the launch (or null).
+// ctl: the control block (OpsCtl).  status: band_lookback_words(n) look-back words; epoch: new per
+// launch.  opsctl: the kernels' flags (SpillCtl).  hctl: pinned host copy of ctl[0 .. kOpsCtl) written
+// by the launch (or null).
 constexpr int kOpsBlockReads = 1024;
-constexpr int kOpsCtl = 10;
-constexpr int kOpsCtlAll = kOpsCtl + 2;
 struct OpsCounts {
-    const int32_t* fallback;   // [0]: exact-kernel reads of the chunk, [3]: look-back error flag
+    const int32_t* fallback;   // the chunk's counters (ChunkCounter): kCntExact, kCntLookback
     const int32_t* redo;       // second band level reads (null: one level)
     const int32_t* band;       // reads that needed the DP (null: not the band path)
     int32_t direct;            // KernelArgs::redo_direct of the chunk (0: off)
-    int32_t one_level;         // the chunk ran the 32-diagonal level alone: its DP reads go to ctl[7]
+    int32_t one_level;         // the chunk ran the 32-diagonal level alone: its DP reads go to kCtlDpOneLevel
     int32_t prio;              // raise the compaction's issue priority (KernelArgs::tail_prio)
     const int32_t* exact;      // the wide level's give-ups: the exact kernel's reads (null: no wide level)
     const int32_t* seeded;     // the seeded reads (to the wide level, or the second level first; null: none)

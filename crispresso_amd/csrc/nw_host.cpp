@@ -84,7 +84,7 @@ struct Scratch {
     DevBuf<uint8_t> d_seed_flags;      // ... per entry: left to the wide level by the 32-diagonal level
     DevBuf<int32_t> d_seed_list2;      // ... those entries, in order (the wide level's seeded list)
     DevBuf<int64_t> d_fallback2;       // reads the wide level gave up on (the exact kernel's list)
-    DevBuf<int32_t> d_fallback_count;  // [0] fallback count, [1] -, [2] redo count
+    DevBuf<int32_t> d_fallback_count;  // the chunk's counters (nw::ChunkCounter)
     DevBuf<int32_t> d_redo;            // reads the first band level could not certify
     DevBuf<uint8_t> d_redo_flags;      // per sorted position: handed to the second level
     DevBuf<int32_t> d_order, d_sort_key;
@@ -164,7 +164,7 @@ static Switches read_switches() {
 // configurations, geometry.  A pooled call keeps one per group and assigns it per chunk.
 struct AmpConfig {
     nw::LaunchCfg cfg{};              // full-storage kernel
-    // certified diagonal-band kernels (nw_band.hip): the default path
+    // certified diagonal-band kernels (nw_band_device.h, the stage files): the default path
     bool use_diag = false;
     nw::LaunchCfg diag_fill{}, diag_walk{};          // 32-diagonal level (the certificate's last resort)
     nw::LaunchCfg diag16_fill{}, diag16_walk{};      // 16-diagonal first level (0 grid: off)
@@ -318,7 +318,7 @@ struct nw_ctx {
     std::vector<hipEvent_t> ev_in, ev_cs, ev_ce, ev_out, ev_bulk;
     hipEvent_t ev_h0 = nullptr;
     hipEvent_t ev_start = nullptr;     // the second compute stream starts after the first's set-up
-    int64_t* h_ctl = nullptr;          // pinned: per chunk ctl[0..3] copied back
+    int64_t* h_ctl = nullptr;          // pinned: per chunk ctl[0, kOpsCtl) copied back
     int64_t h_ctl_chunks = 0;
     float ops_h2d_ms = 0.0f, ops_compute_ms = 0.0f;
     bool call_done = false;            // the last operation was nw_align_ops: the getters report its counts
@@ -655,7 +655,7 @@ int configure_long(nw_ctx* c, Scratch& S, int64_t n, AmpConfig& ac) {
     ac.exact_grid = (int)grid;
     ac.exact_full = true;
     HIP_OR_FAIL(c, S.d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
-    HIP_OR_FAIL(c, S.d_fallback_count.reserve(16));
+    HIP_OR_FAIL(c, S.d_fallback_count.reserve(nw::kChunkCounters));
     return NW_OK;
 }
 
@@ -713,7 +713,7 @@ int configure_wave(nw_ctx* c, const Switches& sw, Scratch& S, int64_t n, AmpConf
     // the exact kernel (nw_align_kernel), which takes both
     if (c->end_weight) {
         HIP_OR_FAIL(c, S.d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
-        HIP_OR_FAIL(c, S.d_fallback_count.reserve(16));
+        HIP_OR_FAIL(c, S.d_fallback_count.reserve(nw::kChunkCounters));
         return NW_OK;
     }
     // certified diagonal band (default): scores and biases within int16, amplicon
@@ -817,7 +817,7 @@ int configure_wave(nw_ctx* c, const Switches& sw, Scratch& S, int64_t n, AmpConf
         }
     }
     HIP_OR_FAIL(c, S.d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
-    HIP_OR_FAIL(c, S.d_fallback_count.reserve(16));
+    HIP_OR_FAIL(c, S.d_fallback_count.reserve(nw::kChunkCounters));
     return NW_OK;
 }
 
@@ -1171,12 +1171,12 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
         // first kernel (nw_band_classify): no memset launches in the chunk's chain
         if (!c->ac.use_diag || p.n <= 0) {
             HIP_OR_FAIL(c, hipMemsetAsync(p.s->d_nops.p, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(p.n, 1), cs));
-            HIP_OR_FAIL(c, hipMemsetAsync(p.s->d_opsctl.p, 0, 2 * sizeof(int32_t), cs));
+            HIP_OR_FAIL(c, hipMemsetAsync(p.s->d_opsctl.p, 0, nw::kSpillCtl * sizeof(int32_t), cs));
         }
     }
     if (c->ac.use_diag) {
         // length sort, certified band fill + walk per pass, exact int32 kernel on the rest
-        if (p.n <= 0) return hipMemsetAsync(p.s->d_fallback_count.p, 0, 16 * sizeof(int32_t), cs) == hipSuccess
+        if (p.n <= 0) return hipMemsetAsync(p.s->d_fallback_count.p, 0, nw::kChunkCounters * sizeof(int32_t), cs) == hipSuccess
                                   ? NW_OK : fail(c, NW_E_HIP, "hipMemsetAsync failed");
         a.lut6 = c->d_lut6.p;
         a.band_order = p.s->d_order.p;
@@ -1187,7 +1187,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
         a.band_maxsub = 5 * c->scale;
         a.band_tab = c->d_btab.p;
         a.sort_key = p.s->d_sort_key.p;
-        a.band_count = p.s->d_fallback_count.p + 1;   // the sort writes the DP count here
+        a.band_count = p.s->d_fallback_count.p + nw::kCntDp;
         a.amp2 = c->cur.amp2;
         a.seed_key = c->cur.seed_key;
         a.seed_pos = c->cur.seed_pos;
@@ -1205,7 +1205,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
             a.seed_info2 = p.s->d_seed2.p;
             a.seed_keys = c->call.seed_keys;
             a.seed_list = p.s->d_seed_list.p;
-            a.seed_count = p.s->d_fallback_count.p + 7;   // zeroed by nw_band_classify
+            a.seed_count = p.s->d_fallback_count.p + nw::kCntSeeded;
         }
         a.lb_status = p.s->d_lb.p;
         a.known2 = p.known ? p.known->d_k2.p : nullptr;
@@ -1230,8 +1230,8 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
                 a.wf_keys = wfk;
                 a.wf_cap = c->ac.wf_cap;
                 a.wf_list = p.s->d_wf_list.p;
-                a.wf_count = p.s->d_fallback_count.p + 11;   // written by the sort
-                a.wf_taken_n = p.s->d_fallback_count.p + 10; // zeroed by nw_band_classify
+                a.wf_count = p.s->d_fallback_count.p + nw::kCntWfCount;
+                a.wf_taken_n = p.s->d_fallback_count.p + nw::kCntWfTaken;
             }
         }
         HIP_OR_FAIL(c, nw::launch_band_sort(a, next_epoch(c), cs));
@@ -1243,7 +1243,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
         // -> level 2 (32 diagonals) -> the exact int32 kernel.  Kernels clamp the pair
         // ranges to the device-side counts.
         a.redo_list = p.s->d_redo.p;
-        a.redo_count = p.s->d_fallback_count.p + 2;
+        a.redo_count = p.s->d_fallback_count.p + nw::kCntRedo;
         if (two) a.redo_flags = p.s->d_redo_flags.p;   // the first level's walk writes every position's
         // a chunk whose first level hands on at most `direct` reads skips the second level on
         // the device: the wide level takes them (up to 1/16 of the chunk, as many as its region
@@ -1280,7 +1280,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
             af.band_pair_lo = 0;
             af.band_pair_hi = c->ac.wf_pairs;
             af.fallback_list = p.s->d_fallback2.p + base;
-            af.fallback_count = p.s->d_fallback_count.p + 6;   // zeroed by nw_band_classify
+            af.fallback_count = p.s->d_fallback_count.p + nw::kCntWideGiveUp;
             HIP_OR_FAIL(c, hipEventRecord(c->ev_wf0, cs));
             HIP_OR_FAIL(c, hipStreamWaitEvent(wf_side, c->ev_wf0, 0));
             HIP_OR_FAIL(c, nw::launch_band(nw::kWideDiags, af, c->ac.wf_fill, c->ac.wf_walk, wf_side, nullptr));
@@ -1331,7 +1331,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
             ac.l1_skip = 0;
             ac.wf_list = nullptr;
             ac.redo_list = p.s->d_seed_list2.p;
-            ac.redo_count = p.s->d_fallback_count.p + 8;   // zeroed by nw_band_classify
+            ac.redo_count = p.s->d_fallback_count.p + nw::kCntSeededL2;
             HIP_OR_FAIL(c, nw::launch_redo_compact(ac, p.n + p.n / 4096 + 2, next_epoch(c), cs, true));
             tmark(c, p, cs, "seed compact");
             a.seed_list = ac.redo_list;
@@ -1339,7 +1339,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
         }
         if (pev) HIP_OR_FAIL(c, hipEventRecord(c->ev_l2, cs));
         a.work_list = a.fallback_list;   // what the 16 / 32 levels could not certify
-        a.work_count = p.s->d_fallback_count.p;
+        a.work_count = p.s->d_fallback_count.p + nw::kCntExact;
         a.redo_direct = direct;
         if (c->ac.wide_fill.grid > 0) {
             // the wide level over that list (and, direct hand-off, the first level's redo list):
@@ -1356,7 +1356,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
             aw.band_pair_lo = 0;
             aw.band_pair_hi = c->ac.wide_pairs;
             aw.fallback_list = p.s->d_fallback2.p + base;
-            aw.fallback_count = p.s->d_fallback_count.p + 6;   // zeroed by nw_band_classify
+            aw.fallback_count = p.s->d_fallback_count.p + nw::kCntWideGiveUp;
             HIP_OR_FAIL(c, nw::launch_band(nw::kWideDiags, aw, c->ac.wide_fill, c->ac.wide_walk, cs, nullptr));
             tmark(c, p, cs, "wide");
             a.work_list = aw.fallback_list;
@@ -1371,7 +1371,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
         tmark(c, p, cs, "exact");
         return NW_OK;
     }
-    HIP_OR_FAIL(c, hipMemsetAsync(p.s->d_fallback_count.p, 0, 16 * sizeof(int32_t), cs));
+    HIP_OR_FAIL(c, hipMemsetAsync(p.s->d_fallback_count.p, 0, nw::kChunkCounters * sizeof(int32_t), cs));
     if (c->ac.exact_full) {   // long amplicon: every read through the multi-wave kernel
         if (p.n > 0)
             HIP_OR_FAIL(c, nw::launch_exact(a, c->ac.exact_grid, c->ac.exact_lds, c->ac.exact_tb_lds, c->ac.exact_slab, false,
@@ -1381,7 +1381,6 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
     if (p.n > 0) HIP_OR_FAIL(c, launch_work(c, a, p.exact_small, cs));   // every read (null work list)
     return NW_OK;
 }
-
 
 // Ops-mode buffers for chunks of up to `chunk` reads of a call over n reads:
 // slots and counts per chunk (reused chunk after chunk, the compaction copies them
@@ -1396,7 +1395,7 @@ int ops_reserve(nw_ctx* c, const Switches& sw, Scratch& S, int64_t chunk, int64_
     HIP_OR_FAIL(c, S.d_slots.reserve((size_t)(2 * chunk * c->ops_slot)));   // column-major + row-major areas
     HIP_OR_FAIL(c, S.d_nops.reserve((size_t)chunk));
     HIP_OR_FAIL(c, S.d_spill.reserve((size_t)c->spill_cap));
-    HIP_OR_FAIL(c, S.d_opsctl.reserve(2));
+    HIP_OR_FAIL(c, S.d_opsctl.reserve(nw::kSpillCtl));
     HIP_OR_FAIL(c, c->d_ctl64.reserve(2 * nw::kOpsCtlAll));   // a dual call: one block per pass
     HIP_OR_FAIL(c, S.d_lb.reserve((size_t)nw::band_lookback_words(chunk)));
     HIP_OR_FAIL(c, c->d_opsoff.reserve((size_t)std::max<int64_t>(n, 1) + 1));
@@ -1406,7 +1405,7 @@ int ops_reserve(nw_ctx* c, const Switches& sw, Scratch& S, int64_t chunk, int64_
 
 // Kernels of p.n reads starting at read `base`, then their compaction into
 // staging[which]: ops_off of those reads (global: the call's running base in
-// ctl[0]) and ctl[1..3] = chunk base, chunk total, error.
+// nw::kCtlTotal) and the chunk's kCtlBase, kCtlChunkTotal, kCtlError.
 int launch_range_ops(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out, hipEvent_t staging_free = nullptr,
                      hipEvent_t prev_done = nullptr, int64_t* hctl = nullptr, int parity = 0,
                      const nw::OpsHostOut* host = nullptr) {
@@ -1423,19 +1422,19 @@ int launch_range_ops(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* o
     cnt.fallback = p.s->d_fallback_count.p;
     cnt.prio = c->tail_prio;
     if (c->ac.use_diag && p.n > 0) {
-        cnt.band = p.s->d_fallback_count.p + 1;
+        cnt.band = p.s->d_fallback_count.p + nw::kCntDp;
         // second-level reads of a two-level chunk; a chunk run on the 32-diagonal level alone
-        // counts its DP reads apart (ctl[7]: the adaptive choice reads two-level chunks only)
-        if (c->ac.diag16_fill.grid > 0 && !p.skip16) cnt.redo = p.s->d_fallback_count.p + 2;
+        // counts its DP reads apart (nw::kCtlDpOneLevel: the adaptive choice reads two-level chunks only)
+        if (c->ac.diag16_fill.grid > 0 && !p.skip16) cnt.redo = p.s->d_fallback_count.p + nw::kCntRedo;
         cnt.one_level = c->ac.diag16_fill.grid > 0 && p.skip16;
         cnt.direct = p.skip16 ? 0 : L.redo_direct;
-        if (c->ac.wide_fill.grid > 0) cnt.exact = p.s->d_fallback_count.p + 6;
+        if (c->ac.wide_fill.grid > 0) cnt.exact = p.s->d_fallback_count.p + nw::kCntWideGiveUp;
         if (L.seed_chunk) {
-            cnt.seeded = p.s->d_fallback_count.p + 7;
-            cnt.seed_pad = p.s->d_fallback_count.p + 9;   // the sort's padding entries (zeroed by classify)
+            cnt.seeded = p.s->d_fallback_count.p + nw::kCntSeeded;
+            cnt.seed_pad = p.s->d_fallback_count.p + nw::kCntSeedPad;
         }
-        if (L.seed_chunk && c->call.seed_l2) cnt.seeded_l2 = p.s->d_fallback_count.p + 8;
-        if (L.wf_chunk) cnt.wide_first = p.s->d_fallback_count.p + 10;
+        if (L.seed_chunk && c->call.seed_l2) cnt.seeded_l2 = p.s->d_fallback_count.p + nw::kCntSeededL2;
+        if (L.wf_chunk) cnt.wide_first = p.s->d_fallback_count.p + nw::kCntWfTaken;
     }
     if (p.n <= 0) cnt.fallback = nullptr;
     nw::OpsKnown kn{};
@@ -1499,16 +1498,16 @@ int ops_events(nw_ctx* c, size_t chunks) {
 }
 
 int ops_error(nw_ctx* c, int64_t err) {
-    if (err & 4) return fail(c, NW_E_HIP, "a device prefix scan waited too long for its predecessor blocks");
-    if (err & 2) return fail(c, NW_E_NOMEM, "ops spill area full: reads with more than %d traceback runs need more "
+    if (err & nw::kOpsErrLookback) return fail(c, NW_E_HIP, "a device prefix scan waited too long for its predecessor blocks");
+    if (err & nw::kOpsErrSpill) return fail(c, NW_E_NOMEM, "ops spill area full: reads with more than %d traceback runs need more "
                                             "than the spill area (%lld MB)", c->ops_slot,
                              (long long)(c->spill_cap * 4 >> 20));
-    if (err & 1) return fail(c, NW_E_NOMEM, "ops staging array full");
+    if (err & nw::kOpsErrStaging) return fail(c, NW_E_NOMEM, "ops staging array full");
     return NW_OK;
 }
 
 // the last resident run's path counters (set 0's d_fallback_count), once it is through
-bool run_counts(nw_ctx* c, int32_t (&fb)[11]) {
+bool run_counts(nw_ctx* c, int32_t (&fb)[nw::kChunkCounters]) {
     (void)hipSetDevice(c->device);
     return hipStreamSynchronize(c->stream) == hipSuccess &&
            hipMemcpy(fb, c->sc[0].d_fallback_count.p, sizeof fb, hipMemcpyDeviceToHost) == hipSuccess;
@@ -1571,9 +1570,9 @@ int nw_batch_download(nw_ctx* c, char* aln_out, int64_t stride, nw_stat* stats) 
     if (c->n == 0) return NW_OK;
     if (aln_out && c->out_mode == NW_OUT_OPS) return fail(c, NW_E_STATE, "ops output: use nw_batch_download_ops");
     if (c->ac.use_diag) {   // the band path's single-pass scans report a cut-off look-back here
-        int32_t fb[4] = {0, 0, 0, 0};
+        int32_t fb[nw::kCntLookback + 1] = {};
         HIP_OR_FAIL(c, hipMemcpy(fb, c->sc[0].d_fallback_count.p, sizeof fb, hipMemcpyDeviceToHost));
-        if (fb[3]) return ops_error(c, 4);
+        if (fb[nw::kCntLookback]) return ops_error(c, nw::kOpsErrLookback);
     }
     if (stats)
         HIP_OR_FAIL(c, hipMemcpy(stats, c->d_stats.p, sizeof(nw::Stat) * (size_t)c->n, hipMemcpyDeviceToHost));
@@ -1642,7 +1641,7 @@ int nw_batch_device_ops(nw_ctx* c, void** d_ops, void** d_ops_off, void** d_stat
     HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
     int64_t ctl[nw::kOpsCtl];
     HIP_OR_FAIL(c, hipMemcpy(ctl, c->d_ctl64.p, sizeof ctl, hipMemcpyDeviceToHost));
-    int rc = ops_error(c, ctl[3]);
+    int rc = ops_error(c, ctl[nw::kCtlError]);
     if (rc) return rc;
     if (!c->bytes_full) {   // a packed batch: classify wrote the DP reads' bytes only; now every read's
         HIP_OR_FAIL(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, c->batch_pos0 / 4, c->batch_base0,
@@ -1676,13 +1675,13 @@ int nw_batch_geometry(const nw_ctx* c, int32_t* rows_per_lane, int32_t* waves_pe
 int64_t nw_batch_fallbacks(nw_ctx* c) {
     if (c && c->call_done) return c->call_counts[3];
     if (!c || !c->ran) return -1;
-    int32_t v[11];
+    int32_t v[nw::kChunkCounters];
     if (!run_counts(c, v)) return -1;
     if (!c->ac.use_diag) return 0;
     // the wide-first launch's reads are the wide level's too; a skipped second level
     // (KernelArgs::redo_direct): its reads went to the exact kernel
     const int direct = c->ac.diag16_fill.grid > 0 ? c->last_launch.redo_direct : 0;
-    return v[0] + v[10] + (direct > 0 && v[2] <= direct ? v[2] : 0);
+    return v[nw::kCntExact] + v[nw::kCntWfTaken] + (direct > 0 && v[nw::kCntRedo] <= direct ? v[nw::kCntRedo] : 0);
 }
 
 int nw_align_batch(nw_ctx* c, const char* reads, const int64_t* offsets, int64_t n, char* aln_out,
@@ -1835,17 +1834,17 @@ int nw_batch_download_ops(nw_ctx* c, uint32_t* ops_out, int64_t ops_cap, int64_t
     HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
     int64_t ctl[nw::kOpsCtl];
     HIP_OR_FAIL(c, hipMemcpy(ctl, c->d_ctl64.p, sizeof ctl, hipMemcpyDeviceToHost));
-    int rc = ops_error(c, ctl[3]);
+    int rc = ops_error(c, ctl[nw::kCtlError]);
     if (rc) return rc;
     if (c->n > 0) {
         if (stats) HIP_OR_FAIL(c, hipMemcpy(stats, c->d_stats.p, sizeof(nw::Stat) * (size_t)c->n, hipMemcpyDeviceToHost));
         if (ops_off) HIP_OR_FAIL(c, hipMemcpy(ops_off, c->d_opsoff.p, sizeof(int64_t) * (size_t)c->n, hipMemcpyDeviceToHost));
     }
-    if (ops_off) ops_off[c->n] = ctl[2];
-    if (ctl[2] > ops_cap)
-        return fail(c, NW_E_CAPACITY, "ops_cap %lld < %lld runs", (long long)ops_cap, (long long)ctl[2]);
-    if (ctl[2] > 0 && ops_out)
-        HIP_OR_FAIL(c, hipMemcpy(ops_out, c->sc[0].d_staging.p, sizeof(uint32_t) * (size_t)ctl[2], hipMemcpyDeviceToHost));
+    if (ops_off) ops_off[c->n] = ctl[nw::kCtlChunkTotal];
+    if (ctl[nw::kCtlChunkTotal] > ops_cap)
+        return fail(c, NW_E_CAPACITY, "ops_cap %lld < %lld runs", (long long)ops_cap, (long long)ctl[nw::kCtlChunkTotal]);
+    if (ctl[nw::kCtlChunkTotal] > 0 && ops_out)
+        HIP_OR_FAIL(c, hipMemcpy(ops_out, c->sc[0].d_staging.p, sizeof(uint32_t) * (size_t)ctl[nw::kCtlChunkTotal], hipMemcpyDeviceToHost));
     return NW_OK;
 }
 
@@ -2041,7 +2040,7 @@ struct OpsCall {
     HostTimer ht;
     // per pass: the caller's outputs, the runs' running total
     nw_stat* st_p[2]; int64_t* oo_p[2]; uint32_t* ops_p[2]; int64_t cap_p[2], total_p[2] = {0, 0};
-    int64_t err = 0;                  // the chunks' ctl[3], or-ed
+    int64_t err = 0;                  // the chunks' kCtlError, or-ed
     bool cap_short = false;
     int64_t chunk = 1;                // reads of a full chunk
     std::vector<Chunk> chunks;
@@ -2307,8 +2306,8 @@ int copy_runs(nw_ctx* c, OpsCall& o, int64_t k) {
     HIP_OR_FAIL(c, hipEventSynchronize(c->ev_ce[(size_t)k]));
     o.ht.lap(5);
     const int64_t* h = c->h_ctl + nw::kOpsCtl * k;
-    o.err |= h[3];
-    const int64_t cb = h[1], tot = h[2];
+    o.err |= h[nw::kCtlError];
+    const int64_t cb = h[nw::kCtlBase], tot = h[nw::kCtlChunkTotal];
     const int pass = o.chunks[(size_t)k].pass;
     uint32_t* po = o.ops_p[pass];
     if (!po) {   // records only (a scores-only pass, CORE:1740-1741): the runs stay on the device
@@ -2410,7 +2409,8 @@ int run_chunk(nw_ctx* c, OpsCall& o, int64_t k) {
     if (o.dual) o.skip16 = false;   // (each chunk decides for its own pass)
     if (o.sw.adapt && jn >= 0) {   // pooled calls too: one library's amplicons, one read source
         if (!o.one_level[(size_t)jn]) {
-            const int64_t dp = (hn[6] - hn[7]) - (hpn[6] - hpn[7]), l2 = hn[5] - hpn[5];
+            const int64_t dp = (hn[nw::kCtlDp] - hn[nw::kCtlDpOneLevel]) - (hpn[nw::kCtlDp] - hpn[nw::kCtlDpOneLevel]);
+            const int64_t l2 = hn[nw::kCtlL2] - hpn[nw::kCtlL2];
             o.skip16 = dp >= 2048 && 2 * l2 > dp;
         } else {
             o.skip16 = (o.in_pass(k) & 3) != 0;
@@ -2429,7 +2429,7 @@ int run_chunk(nw_ctx* c, OpsCall& o, int64_t k) {
     // on a high-priority stream, each chunk's upload split over two streams: +0.01 to +0.58 ms.)
     // the exact kernel's grid: small while the newest chunk read back sent it few reads
     // (after the wide level it gets the rare read no band certifies)
-    p.exact_small = jn < 0 || hn[8] - hpn[8] < 256;
+    p.exact_small = jn < 0 || hn[nw::kCtlReachedExact] - hpn[nw::kCtlReachedExact] < 256;
     // diagnostics: the last chunks' launches
     p.trace = o.sw.trace > 0 && k >= nchunks - o.sw.trace;
     p.chunk = (int)k;
@@ -2475,12 +2475,12 @@ int finish_call(nw_ctx* c, OpsCall& o) {
         while (kl > 0 && o.chunks[(size_t)kl].pass != 0) --kl;
         const int64_t* h = c->h_ctl + nw::kOpsCtl * kl;
         const bool two = o.any_diag && c->ac.diag16_fill.grid > 0;
-        c->call_counts[0] = o.any_diag ? n - h[6] : 0;
-        c->call_counts[1] = two ? h[6] - h[7] : 0;                // first level: two-level chunks' DP reads
-        c->call_counts[2] = o.any_diag ? (two ? h[5] + h[7] : h[6]) : 0;
-        c->call_counts[3] = h[4];
-        c->call_exact = h[8];
-        c->call_wide_first = h[9];
+        c->call_counts[0] = o.any_diag ? n - h[nw::kCtlDp] : 0;
+        c->call_counts[1] = two ? h[nw::kCtlDp] - h[nw::kCtlDpOneLevel] : 0;                // first level: two-level chunks' DP reads
+        c->call_counts[2] = o.any_diag ? (two ? h[nw::kCtlL2] + h[nw::kCtlDpOneLevel] : h[nw::kCtlDp]) : 0;
+        c->call_counts[3] = h[nw::kCtlExact];
+        c->call_exact = h[nw::kCtlReachedExact];
+        c->call_wide_first = h[nw::kCtlWideFirst];
     }
     c->call_done = true;
     // device times: the upload span on s_in, the chunks' compute spans summed
@@ -2960,17 +2960,17 @@ int nw_batch_path_counts(nw_ctx* c, int64_t* counts4) {
         counts4[3] = nw_batch_fallbacks(c);
         return NW_OK;
     }
-    int32_t fb[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, need = 0;
+    int32_t fb[nw::kChunkCounters] = {}, need = 0;
     HIP_OR_FAIL(c, hipMemcpy(fb, c->sc[0].d_fallback_count.p, sizeof fb, hipMemcpyDeviceToHost));
-    need = fb[1];   // the sort's DP count
+    need = fb[nw::kCntDp];
     const bool two = c->ac.diag16_fill.grid > 0;
     counts4[0] = c->n - need;             // exact copies (no DP)
     counts4[1] = two ? need : 0;          // first level (16 diagonals)
     // a skipped second level (KernelArgs::redo_direct) sent its reads to the exact kernel
-    const bool direct = two && c->last_launch.redo_direct > 0 && fb[2] <= c->last_launch.redo_direct;
-    counts4[2] = two ? (direct ? 0 : fb[2]) : need;   // second level (32 diagonals)
+    const bool direct = two && c->last_launch.redo_direct > 0 && fb[nw::kCntRedo] <= c->last_launch.redo_direct;
+    counts4[2] = two ? (direct ? 0 : fb[nw::kCntRedo]) : need;   // second level (32 diagonals)
     // the 16 / 32 levels' give-ups and the wide-first launch's reads (wide level + exact kernel)
-    counts4[3] = fb[0] + (direct ? fb[2] : 0) + fb[10];
+    counts4[3] = fb[nw::kCntExact] + (direct ? fb[nw::kCntRedo] : 0) + fb[nw::kCntWfTaken];
     return NW_OK;
 }
 
@@ -2978,16 +2978,16 @@ int64_t nw_batch_wide_first_reads(nw_ctx* c) {
     if (c && c->call_done) return c->call_wide_first;
     if (!c || !c->ran) return -1;
     if (!c->ac.use_diag) return 0;
-    int32_t fb[11];
-    return run_counts(c, fb) ? fb[10] : -1;
+    int32_t fb[nw::kChunkCounters];
+    return run_counts(c, fb) ? fb[nw::kCntWfTaken] : -1;
 }
 
 int64_t nw_batch_exact_reads(nw_ctx* c) {
     if (c && c->call_done) return c->call_exact;
     if (!c || !c->ran) return -1;
     if (!c->ac.use_diag || c->ac.wide_fill.grid <= 0) return nw_batch_fallbacks(c);
-    int32_t fb[11];
-    return run_counts(c, fb) ? fb[6] : -1;
+    int32_t fb[nw::kChunkCounters];
+    return run_counts(c, fb) ? fb[nw::kCntWideGiveUp] : -1;
 }
 
 }  // extern "C"

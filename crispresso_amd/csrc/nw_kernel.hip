@@ -15,7 +15,7 @@
 //     [code][lane][RP] int8, so one ds_read_b32/b64 yields a lane's R scores.
 //   * traceback: 4 bits per cell (best-state >M, Y>X, X-extend, Y-extend), every
 //     cell stored: in LDS (TB_LDS_FULL) or a per-wave HBM slab (TB_GLOBAL_FULL).
-//     This is the exact fallback of the certified band path (nw_band.hip): the
+//     This is the exact fallback of the certified band path (nw_band_device.h): the
 //     reads no band level certifies, rare codes, -endweight, and every read when
 //     the band does not apply (penalties outside its int16 range).
 //   * the walk is done by the whole wave in runs: 64 lanes test 64 cells of the

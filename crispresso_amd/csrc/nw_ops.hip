@@ -11,7 +11,7 @@
 // and its pinned host mirror (no copy launch in the chunk's chain).  The running base
 // alternates between two words (ctl[kOpsCtl + parity]): chunk k reads one and writes the
 // other, so no block of a launch can see its own chunk's update.
-// The host copies staging[0, ctl[2]) to ops_out + ctl[1].
+// The host copies staging[0, ctl[kCtlChunkTotal]) to ops_out + ctl[kCtlBase].
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -139,25 +139,25 @@ __global__ __launch_bounds__(kOpsThreads) void nw_ops_compact(const int32_t* nop
         off += c;
     }
     if (over) {
-        atomicOr((unsigned long long*)(ctl + 3), 1ull);
-        if (hctl) hctl[3] |= 1;   // every writer sets the same bit over the value the last block left
+        atomicOr((unsigned long long*)(ctl + kCtlError), (unsigned long long)kOpsErrStaging);
+        if (hctl) hctl[kCtlError] |= kOpsErrStaging;   // every writer sets the same bit over the value the last block left
     }
     if (threadIdx.x == 0 && sh_bad) {
-        atomicOr((unsigned long long*)(ctl + 3), 4ull);
-        if (hctl) hctl[3] |= 4;
+        atomicOr((unsigned long long*)(ctl + kCtlError), (unsigned long long)kOpsErrLookback);
+        if (hctl) hctl[kCtlError] |= kOpsErrLookback;
     }
     if (threadIdx.x == 0 && blockIdx.x == gridDim.x - 1) {
         const long long chunk_total = (long long)sh_excl + total;
-        ctl[1] = base;
-        ctl[2] = chunk_total;
+        ctl[kCtlBase] = base;
+        ctl[kCtlChunkTotal] = chunk_total;
         ops_off[n] = base + chunk_total;   // the end of the chunk's last read (the next chunk's first offset)
-        ctl[0] = base + chunk_total;
+        ctl[kCtlTotal] = base + chunk_total;
         ctl[kOpsCtl + (parity ^ 1)] = base + chunk_total;
-        if (opsctl[1]) ctl[3] |= 2;   // a kernel found the spill area full
-        if (cnt.fallback && cnt.fallback[3]) ctl[3] |= 4;   // an aligner kernel's look-back was cut off
+        if (opsctl[kSpillFull]) ctl[kCtlError] |= kOpsErrSpill;   // a kernel found the spill area full
+        if (cnt.fallback && cnt.fallback[kCntLookback]) ctl[kCtlError] |= kOpsErrLookback;   // an aligner kernel's look-back was cut off
         // the call's reads by path, summed over chunks (nw_batch_path_counts after nw_align_ops)
         long long fb = 0;
-        if (cnt.fallback) fb += cnt.fallback[0];
+        if (cnt.fallback) fb += cnt.fallback[kCntExact];
         // a chunk that skipped its second level (KernelArgs::redo_direct) sent the redo
         // list to the exact kernel
         const bool direct = cnt.direct > 0 && cnt.redo && *cnt.redo <= cnt.direct;
@@ -172,14 +172,14 @@ __global__ __launch_bounds__(kOpsThreads) void nw_ops_compact(const int32_t* nop
         nw -= pw;
         n2 -= pad - pw;
         const long long wf1 = cnt.wide_first ? (long long)*cnt.wide_first : 0ll;   // the wide level's reads too
-        ctl[4] += fb + nw + wf1;
-        ctl[9] += wf1;
-        ctl[8] += cnt.exact ? (long long)*cnt.exact : fb;
-        if (cnt.redo && !direct) ctl[5] += *cnt.redo;
-        ctl[5] += n2;
+        ctl[kCtlExact] += fb + nw + wf1;
+        ctl[kCtlWideFirst] += wf1;
+        ctl[kCtlReachedExact] += cnt.exact ? (long long)*cnt.exact : fb;
+        if (cnt.redo && !direct) ctl[kCtlL2] += *cnt.redo;
+        ctl[kCtlL2] += n2;
         const long long dp = (cnt.band ? *cnt.band : 0) + ns - pad;
-        ctl[6] += dp;
-        if (cnt.one_level) ctl[7] += dp;
+        ctl[kCtlDp] += dp;
+        if (cnt.one_level) ctl[kCtlDpOneLevel] += dp;
         if (hctl)
             for (int q = 0; q < kOpsCtl; ++q) hctl[q] = ctl[q];
     }

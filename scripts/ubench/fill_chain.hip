@@ -1,7 +1,7 @@
 // fill_chain.hip -- microbenchmark: issue rate of nw_band_fill<16>'s per-step
 // instruction chain on gfx950 (measure before claiming a floor).
 //
-// The loop body is the fill's step (nw_band.hip, step lambda) with the same
+// The loop body is the fill's step (nw_band_fill.hip, step lambda) with the same
 // dependencies -- DPP row_shr:2 / row_shl:2 of the previous step's values, packed
 // u16 max / add / sub, v_perm + v_and_or for the traceback bits -- but scores come
 // from registers (MODE 0: no LDS), from an LDS table with the fill's random

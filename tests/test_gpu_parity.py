@@ -372,7 +372,7 @@ def test_pooled_multi_amplicon(gpu_aligner_factory, oracle):
     assert_same(oracle, amp, buf, off, al.align_packed(buf, off), "after-multi")
 
 
-# ---------------------------------------------------------------- certified band (nw_band.hip)
+# ---------------------------------------------------------------- certified band (nw_band_device.h, stage files)
 
 @pytest.mark.parametrize("direct", ["0", None])
 def test_diag_is_default_and_certifies_c2(gpu_aligner_factory, oracle, monkeypatch, direct):
