@@ -63,6 +63,12 @@ ALLELE_EXPORTS = (
     "nwa_reads_per_step", "nwa_group_host", "nwa_reads_have_lower",
 )
 
+# Every symbol include/crispr_count.h declares.
+COUNT_EXPORTS = (
+    "nwc_create", "nwc_destroy", "nwc_last_error", "nwc_count", "nwc_fetch_groups", "nwc_last_collided",
+    "nwc_phase_times",
+)
+
 # Every symbol include/crispr_flash.h declares.
 FLASH_EXPORTS = ("nwf_merge_batch", "nwf_last_error")
 
@@ -264,6 +270,15 @@ def load() -> ctypes.CDLL:
         "nwa_group_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p, POINTER(c_int64), c_int32]),
         "nwa_reads_have_lower": (c_int, [c_void_p, c_void_p, c_int64, c_int32]),
+        "nwc_create": (c_int, [c_int, POINTER(c_void_p)]),
+        "nwc_destroy": (None, [ctx_p]),
+        "nwc_last_error": (c_char_p, [ctx_p]),
+        "nwc_count": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_char_p, c_int32, c_int32, c_void_p, c_void_p,
+                              c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]
+                      + [POINTER(c_int64)] * 4 + [POINTER(c_float)]),
+        "nwc_fetch_groups": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64]),
+        "nwc_last_collided": (c_int64, [ctx_p]),
+        "nwc_phase_times": (c_int, [ctx_p, c_void_p]),
         "nw_synth_offsets": (c_int64, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,
                                         c_int32]),
         "nw_synth_reads": (c_int, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,
@@ -306,7 +321,7 @@ def exported_symbols() -> dict:
     """Map of each declared symbol to whether the loaded library exports it."""
     lib = load()
     out = {}
-    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + SYNTH_EXPORTS:
+    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + COUNT_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + SYNTH_EXPORTS:
         try:
             getattr(lib, name)
             out[name] = name not in _MISSING
