@@ -60,7 +60,8 @@ QUANT_EXPORTS = (
 # Every symbol include/crispr_alleles.h declares.
 ALLELE_EXPORTS = (
     "nwa_create", "nwa_destroy", "nwa_last_error", "nwa_group_device", "nwa_last_collided", "nwa_phase_times",
-    "nwa_reads_per_step", "nwa_group_host", "nwa_reads_have_lower",
+    "nwa_reads_per_step", "nwa_group_host", "nwa_reads_have_lower", "nwa_windows_device", "nwa_windows_fetch",
+    "nwa_windows_collided", "nwa_windows_times",
 )
 
 # Every symbol include/crispr_count.h declares.
@@ -270,6 +271,12 @@ def load() -> ctypes.CDLL:
         "nwa_group_host": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_int64,
                                    c_void_p, POINTER(c_int64), c_int32]),
         "nwa_reads_have_lower": (c_int, [c_void_p, c_void_p, c_int64, c_int32]),
+        "nwa_windows_device": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                       c_int32, c_char_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                       c_void_p, c_int32, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+        "nwa_windows_fetch": (c_int, [ctx_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "nwa_windows_collided": (c_int64, [ctx_p]),
+        "nwa_windows_times": (c_int, [ctx_p, c_void_p]),
         "nwc_create": (c_int, [c_int, POINTER(c_void_p)]),
         "nwc_destroy": (None, [ctx_p]),
         "nwc_last_error": (c_char_p, [ctx_p]),

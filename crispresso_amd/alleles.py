@@ -13,12 +13,22 @@ the reference's own last steps on that small frame.
   lowercase byte (the device bytes are upper case, ``align_seq`` keeps the text), else the host
 * :func:`allele_table`       -- groups + ops + ``nwq_read`` results -> ``df_alleles``
 * :func:`merge_allele_tables` -- tables of several batches (forward + RC retry, shards) -> one
+
+The table around a cut site (``Alleles_frequency_table_around_cut_site_for_<sgRNA>.txt``,
+CORE:801-836, 3642-3657) regroups the alleles by a ``2 * offset``-column window.  That window is
+a function of a read's runs, its bytes and the amplicon, so it is cut and grouped per read in
+HBM (crispresso_amd/csrc/nw_windows.hip) and strings are built for the window groups only.
+
+* :func:`around_cut_from_alleles` -- ``get_dataframe_around_cut`` on a ``df_alleles`` (no GPU)
+* :func:`around_cut_tables`       -- one frame per cut point: from the resident batch when the
+  device path takes the arguments, else ``allele_table`` + ``around_cut_from_alleles``
+* :func:`merge_around_cut_tables` -- around-cut tables of several batches -> one
 """
 from __future__ import annotations
 
 import ctypes
 from dataclasses import dataclass
-from typing import Dict, Optional, Sequence
+from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 import pandas as pd
@@ -44,6 +54,33 @@ class ReadGroups:
 
     def __len__(self) -> int:
         return len(self.first)
+
+
+@dataclass
+class WindowGroups:
+    """Groups of the kept reads' windows around one cut point, in order of first appearance."""
+
+    win: np.ndarray                        # uint8 [groups][2][2 * offset]: aligned-read row, reference row, zero-padded
+    win_len: np.ndarray                    # int32 [groups]
+    first: np.ndarray                      # int64 [groups]
+    count: np.ndarray                      # int64 [groups]
+    unedited: np.ndarray                   # uint8 [groups]: a read of the group is UNMODIFIED
+    group_of_read: Optional[np.ndarray]    # int32 [n] (-1: not kept), when asked for
+    collided: int = 0                      # records of the call the device pass left to the host
+
+    def __len__(self) -> int:
+        return len(self.first)
+
+
+def _results_array(read_results, n: int) -> np.ndarray:
+    """The ``[n][4]`` int32 array of ``nwq_read`` from it or from its structured form."""
+    rr = np.asarray(read_results)
+    if rr.dtype.names:
+        rr = np.ascontiguousarray(rr).view(np.int32)
+    rr = np.ascontiguousarray(rr, dtype=np.int32).reshape(-1, 4)
+    if len(rr) != n:
+        raise AlleleError(f"{len(rr)} read results for {n} reads")
+    return rr
 
 
 def _host_arrays(n: int, keep, tag):
@@ -130,6 +167,50 @@ class GpuAlleleGrouper:
             raise AlleleError(f"nwa_group_device failed ({rc}): {msg}")
         self.last_kernel_ms = ms.value
         return ReadGroups(first, count, gor, int(self._lib.nwa_last_collided(self._ctx)))
+
+    def window_times(self) -> Dict[str, float]:
+        """Device ms of the last :meth:`windows` by phase (summed over its cut points)."""
+        ms = np.zeros(3, np.float32)
+        self._lib.nwa_windows_times(self._ctx, _lib.ptr(ms))
+        return dict(zip(("extract", "group", "finish"), (float(x) for x in ms)))
+
+    def windows(self, dev: dict, n: int, awidth: int, amplicon: str, cut_points: Sequence[int], offset: int,
+                read_results, keep=None, tag=None, want_group_of_read: bool = False) -> List[WindowGroups]:
+        """The window groups of a device-resident batch, one :class:`WindowGroups` per cut point
+        (nwa_windows_device): ``dev`` is ``GpuAligner.device_ops()``.  Raises :class:`AlleleError`
+        when a kept read's columns do not hold a cut point (the reference's ``ValueError``) or the
+        arguments are outside what the device path takes (:func:`windows_on_device`)."""
+        n = int(n)
+        keep, tag = _host_arrays(n, keep, tag)
+        rr = _results_array(read_results, n)
+        cuts = np.ascontiguousarray(cut_points, dtype=np.int32)
+        ng = np.zeros(max(len(cuts), 1), np.int64)
+        bad, first_bad = ctypes.c_int64(), ctypes.c_int64()
+        amp = amplicon.encode("ascii")
+        rc = self._lib.nwa_windows_device(self._ctx, dev["ops"], dev["ops_off"], dev["stats"], dev["reads"],
+                                          dev["offsets"], int(dev["reads_bias"]), n, int(awidth), amp, len(amp),
+                                          _lib.ptr(cuts), len(cuts), int(offset), _lib.ptr(keep), _lib.ptr(tag),
+                                          _lib.ptr(rr), int(want_group_of_read), _lib.ptr(ng), ctypes.byref(bad),
+                                          ctypes.byref(first_bad))
+        if rc != 0:
+            msg = self._lib.nwa_last_error(self._ctx).decode(errors="replace")
+            raise AlleleError(f"nwa_windows_device failed ({rc}): {msg}")
+        if bad.value:
+            raise AlleleError(f"{bad.value} kept reads have no column for the cut point in their first "
+                              f"min(aln_len, awidth) columns; the first is read {first_bad.value}")
+        collided = int(self._lib.nwa_windows_collided(self._ctx))
+        out = []
+        for k in range(len(cuts)):
+            g = int(ng[k])
+            w = WindowGroups(np.zeros((g, 2, 2 * int(offset)), np.uint8), np.zeros(g, np.int32), np.zeros(g, np.int64),
+                             np.zeros(g, np.int64), np.zeros(g, np.uint8),
+                             np.empty(n, np.int32) if want_group_of_read else None, collided)
+            rc = self._lib.nwa_windows_fetch(self._ctx, k, _lib.ptr(w.win), _lib.ptr(w.win_len), _lib.ptr(w.first),
+                                             _lib.ptr(w.count), _lib.ptr(w.unedited), _lib.ptr(w.group_of_read))
+            if rc != 0:
+                raise AlleleError(f"nwa_windows_fetch({k}) failed ({rc})")
+            out.append(w)
+        return out
 
 
 _DEFAULT: Dict[int, GpuAlleleGrouper] = {}
@@ -261,3 +342,143 @@ def merge_allele_tables(tables: Sequence[pd.DataFrame]) -> pd.DataFrame:
     if not tables:
         return _finish(pd.DataFrame({k: [] for k in KEYS + ["#Reads"]}).astype({"#Reads": np.int64}))
     return _finish(pd.concat([t[KEYS + ["#Reads"]] for t in tables], ignore_index=True))
+
+
+# ------------------------------------------------------------------ the table around a cut site
+
+AROUND_COLUMNS = ["Reference_Sequence", "Unedited", "%Reads", "#Reads"]
+WINDOW_MAX_OFFSET = 64          # nwa_windows_device's limits (include/crispr_alleles.h)
+WINDOW_MAX_AMPLICON = 16384
+_COUNTED = frozenset("ATCGN")
+
+
+def ref_positions(ref_seq: str) -> List[int]:
+    """CORE:2055-2067: a column whose reference byte is one of ``A T C G N`` gets the number of
+    such columns before it; every other column (``-``, IUPAC, lower case) gets minus that
+    number, or -1 while it is 0."""
+    out, idx = [], 0
+    for c in ref_seq:
+        if c in _COUNTED:
+            out.append(idx)
+            idx += 1
+        else:
+            out.append(-idx if idx else -1)
+    return out
+
+
+def _finish_around(aligned, reference, unedited, reads) -> pd.DataFrame:
+    """Windows with their counts -> the frame of ``get_dataframe_around_cut`` (CORE:812-836):
+    grouped by the two windows, ``#Reads`` summed, ``Unedited`` ORed, ``%Reads`` = ``#Reads`` /
+    total * 100, sorted by ``#Reads`` descending, then the two windows ascending (the reference
+    sorts by ``%Reads`` with an unstable sort: its order of ties is undefined)."""
+    frame = pd.DataFrame({"Aligned_Sequence": np.asarray(aligned, dtype=object),
+                          "Reference_Sequence": np.asarray(reference, dtype=object),
+                          "Unedited": np.asarray(unedited, dtype=bool),
+                          "#Reads": np.asarray(reads, dtype=np.int64)})
+    g = frame.groupby(["Aligned_Sequence", "Reference_Sequence"], sort=True).agg({"Unedited": "any", "#Reads": "sum"})
+    g = g.reset_index()
+    g["Unedited"] = g["Unedited"].astype(bool)
+    g["#Reads"] = g["#Reads"].astype(np.int64)
+    total = int(g["#Reads"].sum())
+    g["%Reads"] = g["#Reads"] / total * 100.0 if total else g["#Reads"].astype(np.float64)
+    g = g.sort_values(by=["#Reads", "Aligned_Sequence", "Reference_Sequence"], ascending=[False, True, True],
+                      kind="stable")
+    return g.set_index("Aligned_Sequence")[AROUND_COLUMNS]
+
+
+def around_cut_from_alleles(df_alleles: pd.DataFrame, cut_point: int, offset: int) -> pd.DataFrame:
+    """``get_dataframe_around_cut(df_alleles, cut_point, offset)`` (CORE:801-836) on a
+    ``df_alleles`` as :func:`allele_table` returns it; no GPU.  ``ref_positions`` comes from
+    ``Reference_Sequence`` (:func:`ref_positions`); the cut column is the first whose value is
+    ``cut_point``, and the window is ``s[cut_idx - offset + 1 : cut_idx + offset + 1]`` under
+    Python's slice rules, as the reference writes it.  An allele without such a column (its
+    reference row was cut before it) is the reference's ``ValueError``: :class:`AlleleError`."""
+    cut_point, offset = int(cut_point), int(offset)
+    aligned = df_alleles["Aligned_Sequence"].tolist()
+    reference = df_alleles["Reference_Sequence"].tolist()
+    cut_of: Dict[str, int] = {}
+    wa, wr = [], []
+    for q, (a, r) in enumerate(zip(aligned, reference)):
+        cut_idx = cut_of.get(r)
+        if cut_idx is None:
+            try:
+                cut_idx = ref_positions(r).index(cut_point)
+            except ValueError:
+                raise AlleleError(f"allele {q} ({a[:40]!r}...) has no column for cut point {cut_point} in its "
+                                  f"{len(r)} reference columns") from None
+            cut_of[r] = cut_idx
+        lo, hi = cut_idx - offset + 1, cut_idx + offset + 1
+        wa.append(a[lo:hi])
+        wr.append(r[lo:hi])
+    return _finish_around(wa, wr, df_alleles["UNMODIFIED"].to_numpy(dtype=bool), df_alleles["#Reads"].to_numpy())
+
+
+def merge_around_cut_tables(tables: Sequence[pd.DataFrame]) -> pd.DataFrame:
+    """One around-cut table from the tables of several batches for the same cut point and
+    offset (forward + RC retry, shards, pooled parts): ``#Reads`` summed, ``Unedited`` ORed,
+    ``%Reads`` recomputed, sorted again."""
+    tables = [t.reset_index() for t in tables if t is not None and len(t)]
+    if not tables:
+        return _finish_around([], [], [], [])
+    t = pd.concat(tables, ignore_index=True)
+    return _finish_around(t["Aligned_Sequence"], t["Reference_Sequence"], t["Unedited"], t["#Reads"])
+
+
+def windows_on_device(amplicon: str, cut_points: Sequence[int], offset: int) -> bool:
+    """Whether nwa_windows_device takes these: 1 <= offset <= 64, every cut point inside the
+    amplicon, an amplicon of upper-case ``A C G T N`` only that fits the kernel's LDS."""
+    return (1 <= int(offset) <= WINDOW_MAX_OFFSET and 0 < len(amplicon) <= WINDOW_MAX_AMPLICON and
+            set(amplicon) <= set("ACGTN") and all(0 <= int(c) < len(amplicon) for c in cut_points))
+
+
+def around_cut_tables(aligner, amplicon: str, buf: np.ndarray, offsets: np.ndarray, read_results,
+                      cut_points: Sequence[int], offset: int = 20, keep=None, tag=None, *, ops_batch=None,
+                      dev: Optional[dict] = None, nthreads: int = 0) -> List[pd.DataFrame]:
+    """``Alleles_frequency_table_around_cut_site_for_<sgRNA>`` (CORE:3642-3657) for every cut
+    point: one frame per cut point in the form of :func:`around_cut_from_alleles`.
+
+    From the device (crispresso_amd/csrc/nw_windows.hip), with strings for the window groups
+    only, when ``aligner`` holds the batch resident (``device_ops()``; or ``dev`` gives the
+    device arrays of a pass that left none, e.g. a pooled one), no read has a lowercase byte
+    and :func:`windows_on_device` holds.  Otherwise :func:`allele_table` +
+    :func:`around_cut_from_alleles` on ``ops_batch`` (default: ``aligner.download_ops``).
+    ``read_results``: the ``[n][4]`` ``nwq_read`` array; ``keep`` / ``tag`` as
+    :func:`group_reads` takes them."""
+    offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+    buf = np.ascontiguousarray(buf, dtype=np.uint8)
+    n = len(offsets) - 1
+    keep, tag = _host_arrays(n, keep, tag)
+    rr = _results_array(read_results, n)
+    cuts = [int(c) for c in cut_points]
+    kept = np.ones(n, bool) if keep is None else keep != 0
+    if not kept.any():
+        return [_finish_around([], [], [], []) for _ in cuts]
+    if (rr[kept, 0] < 0).any():
+        bad = np.flatnonzero(kept & (rr[:, 0] < 0))[:5].tolist()
+        raise AlleleError(f"reads are not aligned to the amplicon (LEN_AMPLICON bases): {bad}")
+    device = getattr(aligner, "device", 0) if aligner is not None else 0
+    awidth = ops_batch.awidth if ops_batch is not None else getattr(getattr(aligner, "options", None), "awidth", None)
+    if awidth is not None and windows_on_device(amplicon, cuts, offset) and not reads_have_lower(buf, offsets):
+        if dev is None and aligner is not None and hasattr(aligner, "device_ops"):
+            from .aligner import NeedleError
+
+            try:
+                dev = aligner.device_ops()
+            except NeedleError:      # no resident ops-mode batch
+                dev = None
+        if dev is not None:
+            from .needle import _rows_to_str
+
+            out = []
+            for w in default_grouper(device).windows(dev, n, awidth, amplicon, cuts, offset, rr, keep, tag):
+                lens = w.win_len.astype(np.int64)
+                out.append(_finish_around(_rows_to_str(w.win[:, 0, :], lens), _rows_to_str(w.win[:, 1, :], lens),
+                                          w.unedited, w.count))
+            return out
+    if ops_batch is None:
+        if aligner is None or not hasattr(aligner, "download_ops"):
+            raise AlleleError("the host path needs the batch's OpsBatch (ops_batch) or an aligner that holds it")
+        ops_batch = aligner.download_ops(n)
+    groups = group_reads_host(buf, offsets, keep, tag) if dev is not None else group_reads(aligner, buf, offsets, keep, tag)
+    table = allele_table(amplicon, buf, offsets, ops_batch, rr, groups, nthreads)
+    return [around_cut_from_alleles(table, c, offset) for c in cuts]

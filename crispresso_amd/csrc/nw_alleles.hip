@@ -30,9 +30,8 @@
 #include <utility>
 #include <vector>
 
-#include "../../include/crispr_alleles.h"
-#include "../../include/crispr_nw.h"
 #include "host_pool.h"
+#include "nwa_device.h"
 
 namespace nwa {
 
@@ -277,11 +276,6 @@ __global__ __launch_bounds__(256) void assign_kernel(Args a) {
     if (r < a.n) a.gor[r] = a.hash[r] ? (int32_t)a.gid[a.slot[r]] : -1;
 }
 
-struct CollInfo {
-    int64_t start, len;        // the read's bytes at reads + start
-    int32_t tag, group;        // its slot's group
-};
-
 __global__ __launch_bounds__(256) void coll_info_kernel(Args a, const uint32_t* list, int64_t m, CollInfo* out) {
     const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (i >= m) return;
@@ -294,62 +288,11 @@ __global__ __launch_bounds__(256) void coll_info_kernel(Args a, const uint32_t* 
     out[i] = c;
 }
 
-template <class T>
-struct Buf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        release();
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 }  // namespace nwa
-
-struct nwa_ctx {
-    int device = 0;
-    int num_cus = 256;
-    int hash_bits = 64;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {};
-    std::string err;
-    int64_t collided = 0;
-    float phase_ms[4] = {0, 0, 0, 0};
-    nwa::Buf<uint8_t> d_keep, d_is_first;
-    nwa::Buf<int32_t> d_tag, d_gor;
-    nwa::Buf<uint64_t> d_hash;
-    nwa::Buf<unsigned long long> d_key;
-    nwa::Buf<uint32_t> d_slot, d_first, d_count, d_gid, d_coll, d_counters, d_tile_sum, d_tile_off, d_gfirst, d_gcount;
-    nwa::Buf<nwa::CollInfo> d_info;
-};
 
 namespace {
 
-int afail(nwa_ctx* c, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
-}
-
-#define AHIP(c, expr)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return afail((c), e_ == hipErrorOutOfMemory ? NW_E_NOMEM : NW_E_HIP, "%s: %s", #expr, \
-                         hipGetErrorString(e_));                                                  \
-    } while (0)
+using nwa::afail;
 
 // Groups of the collided reads (sorted by read index) by (tag, bytes), in order of first
 // appearance: grp[i] = the group of collided read i, gfirst / gcount per group.
@@ -431,6 +374,7 @@ void nwa_destroy(nwa_ctx* c) {
     c->d_gfirst.release();
     c->d_gcount.release();
     c->d_info.release();
+    nwa::windows_release(c);
     for (hipEvent_t e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);

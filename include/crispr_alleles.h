@@ -70,6 +70,52 @@ int nwa_group_host(const char* reads, const int64_t* offsets, int64_t n, const u
  * while align_seq keeps the text, so such batches are grouped by nwa_group_host. */
 int nwa_reads_have_lower(const char* reads, const int64_t* offsets, int64_t n, int32_t nthreads);
 
+/* The allele table around a cut site (get_row_around_cut / get_dataframe_around_cut,
+ * CRISPRessoCORE.py:801-836) of a device-resident ops-mode batch, per cut point, without a
+ * string for any full-length allele (crispresso_amd/csrc/nw_windows.hip).
+ *
+ * d_ops / d_ops_off / d_stats / d_reads / d_offsets / reads_bias: nw_batch_device_ops' DEVICE
+ * arrays of the n reads (runs type << 28 | length, their offsets, the nw_stat records, the read
+ * bytes); awidth: the columns parse_needle_output keeps (needle -awidth3).  amplicon: HOST
+ * bytes, amp_len of them, every one of A C G T N.  cut_points: HOST int32 [n_cuts], each in
+ * [0, amp_len); 1 <= offset <= 64; amp_len <= 16384.  Anything else is NW_E_UNSUPPORTED: the
+ * caller takes allele_table + around_cut_from_alleles (crispresso_amd/alleles.py).  keep / tag:
+ * HOST arrays or NULL, as nwa_group_device takes them.  read_results: the HOST [n][4] int32
+ * array of nwq_read (cls first; cls == 0 is UNMODIFIED).
+ *
+ * The window of a kept read for cut point p is columns [cut_idx - offset + 1, cut_idx + offset + 1)
+ * of its aligned-read row and of its reference row, both cut to min(aln_len, awidth) columns,
+ * under Python's slice rules (a negative start counts from the end, a stop past the end is
+ * clipped); cut_idx is the column that holds amplicon base p.  Windows are grouped by
+ * (tag, length, both rows) in order of first appearance, exactly (collided records go through
+ * nwa_group_device's host path).
+ *
+ * *n_no_cut = the kept (cut point, read) pairs whose first min(aln_len, awidth) columns do not
+ * hold base p (the reference's ValueError), *first_no_cut = the smallest such read (-1: none).
+ * When there is one, NW_OK is returned, n_groups is all zero and nothing is kept for
+ * nwa_windows_fetch.  Otherwise n_groups[k] = the groups of cut point k, kept on the context
+ * until its next nwa_windows_device.  Cut points beyond what one launch takes are looped here.
+ * Synchronous. */
+int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_off, const void* d_stats,
+                       const uint8_t* d_reads, const int64_t* d_offsets, int64_t reads_bias, int64_t n, int32_t awidth,
+                       const char* amplicon, int32_t amp_len, const int32_t* cut_points, int32_t n_cuts, int32_t offset,
+                       const uint8_t* keep, const int32_t* tag, const int32_t* read_results, int32_t want_group_of_read,
+                       int64_t* n_groups, int64_t* n_no_cut, int64_t* first_no_cut);
+
+/* The groups of cut point k of the last nwa_windows_device into HOST arrays (any may be NULL):
+ * win uint8 [groups][2][2 * offset] (the aligned-read row, then the reference row, zero-padded
+ * past win_len), win_len int32, first / count int64, unedited uint8 (some read of the group has
+ * cls == 0), group_of_read int32 [n] (-1: not kept; NW_E_STATE unless want_group_of_read was set). */
+int nwa_windows_fetch(const nwa_ctx* c, int32_t k, uint8_t* win, int32_t* win_len, int64_t* first, int64_t* count,
+                      uint8_t* unedited, int32_t* group_of_read);
+
+/* Records of the last nwa_windows_device that went through the exact host path, over its cut points. */
+int64_t nwa_windows_collided(const nwa_ctx* c);
+
+/* Device time of the last nwa_windows_device: ms[0] extract, ms[1] grouping (hash .. compaction),
+ * ms[2] unedited + gather.  A diagnostic (scripts/bench_around_cut.py). */
+int nwa_windows_times(const nwa_ctx* c, float* ms);
+
 #ifdef __cplusplus
 }
 #endif
