@@ -107,7 +107,7 @@ def every_read_records(stats: np.ndarray, ref: np.ndarray) -> int:
     return int(bad.sum())
 
 
-def every_read_multi(amplicons, buf, offsets, which, ob: OpsBatch, threads: int = 16) -> dict:
+def every_read_multi(amplicons, buf, offsets, which, ob: OpsBatch, threads: int = 16, oracle_params=None) -> dict:
     """every_read over a pooled batch grouped by amplicon (which non-decreasing)."""
     offsets = np.asarray(offsets, dtype=np.int64)
     out = {"reads": 0, "distinct": 0, "mismatches": 0, "first_bad": []}
@@ -119,7 +119,7 @@ def every_read_multi(amplicons, buf, offsets, which, ob: OpsBatch, threads: int 
         sub_off = offsets[lo:hi + 1] - offsets[lo]
         r0, r1 = int(ob.ops_off[lo]), int(ob.ops_off[hi])
         sub = OpsBatch(ob.stats[lo:hi], ob.ops[r0:r1], ob.ops_off[lo:hi + 1] - r0, np.diff(sub_off), ob.scale)
-        res = every_read(amp, buf[offsets[lo]:offsets[hi]], sub_off, sub, threads)
+        res = every_read(amp, buf[offsets[lo]:offsets[hi]], sub_off, sub, threads, oracle_params=oracle_params)
         out["reads"] += res["reads"]
         out["distinct"] += res["distinct"]
         out["mismatches"] += res["mismatches"]

@@ -24,8 +24,11 @@ def diag_info(amp, r, d):
     return min(len(pos), 3), f1, f2, g1, g2, pos
 
 
-def certified(amp, r):
+def certified(amp, r, M=M, X=X, O=O, E=E):
+    """The checks at match M, mismatch -X, gap open O and extend E (scaled; the module's by default).  They
+    stand for the certificate only where classify's gate sub3_ok holds (tests/penalty_cases.gates)."""
     La = len(amp)
+    D3 = 3 * (M + X)
     if len(r) != La:
         return False
     info = {d: diag_info(amp, r, d) for d in range(-5, 6)}

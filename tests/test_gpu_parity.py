@@ -15,7 +15,7 @@ pytestmark = pytest.mark.gpu
 # The kernel families production selects: "diag" = the certified band
 # levels + the exact kernel on what they hand on (the default); "full" = the exact
 # int32 kernel on every read (what runs when the band does not apply: -endweight,
-# penalties outside the band's int16 range).
+# penalties outside the band's int16 range: tests/test_gpu_penalties.py runs those).
 KERNELS = ["diag", "full"]
 
 
@@ -323,7 +323,9 @@ def test_band_multiple_passes(gpu_aligner_factory, oracle, monkeypatch):
 
 
 def test_needle_cli_matches_oracle_cli(tmp_path, oracle):
-    """The GPU `needle` shim and the oracle CLI print the same srspair blocks."""
+    """The GPU `needle` shim and the oracle CLI print the same srspair blocks: at the default
+    penalties, at -gapopen=12 -gapextend=1 (scale 1: a score line with one decimal) and at
+    -gapextend=0.25 (scale 4)."""
     import subprocess
     import sys
 
@@ -332,14 +334,18 @@ def test_needle_cli_matches_oracle_cli(tmp_path, oracle):
     reads = synth.unpack(buf, off)
     (tmp_path / "a.fa").write_text(f">AMPL\n{amp}\n")
     fasta = "".join(f">@M0_1_{k} 1_N\n{r}\n" for k, r in enumerate(reads))
-    args = [f"-asequence={tmp_path / 'a.fa'}", "-bsequence=/dev/stdin", "-outfile=/dev/stdout",
-            "-gapopen=10", "-gapextend=0.5", "-awidth3=5000"]
     import os
     shim = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "crispresso_amd", "bin", "needle")
-    gpu = subprocess.run([sys.executable, shim] + args, input=fasta, capture_output=True, text=True, check=True).stdout
-    cpu = subprocess.run([oracle.CLI] + args, input=fasta, capture_output=True, text=True, check=True).stdout
     strip = lambda t: t[t.index("#=="): t.rindex("#---------------------------------------\n#---")]  # noqa: E731
-    assert strip(gpu) == strip(cpu)
+    for penalties in (["-gapopen=10", "-gapextend=0.5"], ["-gapopen=12", "-gapextend=1"],
+                      ["-gapopen=10", "-gapextend=0.25"]):
+        args = [f"-asequence={tmp_path / 'a.fa'}", "-bsequence=/dev/stdin", "-outfile=/dev/stdout"] + penalties + [
+            "-awidth3=5000"]
+        gpu = subprocess.run([sys.executable, shim] + args, input=fasta, capture_output=True, text=True,
+                             check=True).stdout
+        cpu = subprocess.run([oracle.CLI] + args, input=fasta, capture_output=True, text=True, check=True).stdout
+        assert strip(gpu) == strip(cpu), penalties
+        assert "# Score: " in strip(gpu)
 
 
 def test_pooled_multi_amplicon(gpu_aligner_factory, oracle):
