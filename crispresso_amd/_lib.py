@@ -70,6 +70,15 @@ COUNT_EXPORTS = (
     "nwc_phase_times",
 )
 
+# Every symbol include/crispr_regions.h declares.
+REGION_EXPORTS = (
+    "nwr_read_bam", "nwr_bam_free", "nwr_bam_count", "nwr_bam_data", "nwr_bam_offsets", "nwr_bam_n_ref",
+    "nwr_bam_ref_names", "nwr_bam_ref_lens", "nwr_bam_text", "nwr_create", "nwr_destroy", "nwr_last_error",
+    "nwr_extract", "nwr_fetch", "nwr_release",
+)
+NWR_MAX_REGIONS = 1 << 20
+NWR_BY_REFERENCE, NWR_EQX_AS_MATCH = 1, 2
+
 # Every symbol include/crispr_flash.h declares.
 FLASH_EXPORTS = ("nwf_merge_batch", "nwf_last_error")
 
@@ -114,6 +123,17 @@ class NwpResult(ctypes.Structure):
     """nwp_result (include/crispr_front.h)."""
     _fields_ = [("n", c_int64), ("m", c_int64), ("total", c_int64), ("n_exc", c_int64), ("counts", c_int64 * 5),
                 ("trim", c_int64 * 4), ("kernel_ms", c_float * 5), ("handle", c_void_p)]
+
+
+class NwrRegion(ctypes.Structure):
+    """nwr_region (include/crispr_regions.h)."""
+    _fields_ = [("bpstart", c_int64), ("bpend", c_int64), ("ref_id", c_int32), ("reserved", c_int32)]
+
+
+class NwrResult(ctypes.Structure):
+    """nwr_result (include/crispr_regions.h)."""
+    _fields_ = [("n_regions", c_int64), ("n_hits", c_int64), ("n_bytes", c_int64), ("n_no_seq", c_int64),
+                ("kernel_ms", c_float), ("upload_ms", c_float), ("handle", c_void_p)]
 
 
 NWP_FILTERED, NWP_TRIMMED, NWP_NOT_COMBINED, NWP_COMBINED, NWP_COMBINED_OUTIE = range(5)
@@ -286,6 +306,21 @@ def load() -> ctypes.CDLL:
         "nwc_fetch_groups": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64]),
         "nwc_last_collided": (c_int64, [ctx_p]),
         "nwc_phase_times": (c_int, [ctx_p, c_void_p]),
+        "nwr_read_bam": (c_int, [c_char_p, c_void_p, c_int64, POINTER(c_void_p), c_char_p, c_int64]),
+        "nwr_bam_free": (None, [c_void_p]),
+        "nwr_bam_count": (c_int64, [c_void_p]),
+        "nwr_bam_data": (c_void_p, [c_void_p, POINTER(c_int64)]),
+        "nwr_bam_offsets": (c_void_p, [c_void_p]),
+        "nwr_bam_n_ref": (c_int32, [c_void_p]),
+        "nwr_bam_ref_names": (c_void_p, [c_void_p, POINTER(c_int64)]),
+        "nwr_bam_ref_lens": (c_void_p, [c_void_p]),
+        "nwr_bam_text": (c_void_p, [c_void_p, POINTER(c_int64)]),
+        "nwr_create": (c_int, [c_int, POINTER(c_void_p)]),
+        "nwr_destroy": (None, [ctx_p]),
+        "nwr_last_error": (c_char_p, [ctx_p]),
+        "nwr_extract": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_int32, POINTER(NwrResult)]),
+        "nwr_fetch": (c_int, [POINTER(NwrResult)] + [c_void_p] * 7),
+        "nwr_release": (None, [POINTER(NwrResult)]),
         "nw_synth_offsets": (c_int64, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,
                                         c_int32]),
         "nw_synth_reads": (c_int, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,
@@ -328,7 +363,7 @@ def exported_symbols() -> dict:
     """Map of each declared symbol to whether the loaded library exports it."""
     lib = load()
     out = {}
-    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + COUNT_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + SYNTH_EXPORTS:
+    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + COUNT_EXPORTS + REGION_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + SYNTH_EXPORTS:
         try:
             getattr(lib, name)
             out[name] = name not in _MISSING

@@ -1,0 +1,111 @@
+/* crispr_regions.h -- C ABI of the MI355X BAM-to-target reads: a BAM's records become the reads
+ * of every target region (CRISPRessoWGS) or of every reference (CRISPRessoPooled, amplicon mode).
+ *
+ * Replaces the per-read loop of write_trimmed_fastq / get_reference_positions
+ * (CRISPResso/CRISPRessoWGSCORE.py:166-221) and the `samtools view -F 4 | awk` demultiplex of
+ * CRISPRessoPooledCORE.py:870-878.
+ *
+ * The CIGAR walk gives every query base a reference position or none.  pos is BAM's pos + 1; in
+ * the order of the ops:
+ *   M           the next len query bases sit on pos, pos + 1, ...; pos += len
+ *   I, S        the next len query bases sit on nothing
+ *   D, N        pos += len
+ *   H, P, =, X  nothing: neither side advances (the reference's regular expression cannot match
+ *               '=' and its if-chain has no branch for X; NWR_EQX_AS_MATCH treats both as M)
+ * A record hits region (ref_id, bpstart, bpend) iff flag & 4 == 0, its reference is ref_id, and
+ * both bpstart and bpend are positions of one of its query bases.  st / en are the query indices
+ * of bpstart / bpend (the positions increase strictly, so both are unique); the read is
+ * seq[st:en] and qual[st:en] under Python's slice rule (cut to l_seq, empty when en <= st; an
+ * empty read is still a hit).  A region's hits come in record order; regions may overlap or
+ * repeat, each is independent.  With NWR_BY_REFERENCE every record with flag & 4 == 0 and
+ * ref_id >= 0 goes to its reference's set whole (st = 0, en = l_seq).
+ *
+ * The one deliberate difference: a hit of a record without sequence (l_seq == 0) or without
+ * qualities (first quality byte 0xFF), where SAM text has "*" and the reference slices the "*",
+ * is dropped and counted in n_no_seq.
+ *
+ * Sequence bytes are "=ACMGRSVTWYHKDBN"[nibble] as stored (no strand handling), qualities are
+ * stored + 33.  The result is a function of the input alone.  More than 65535 CIGAR ops (the CG
+ * tag) are not looked up: the record is walked by the ops of its core CIGAR.  The binding is
+ * crispresso_amd/regions.py (ctypes).  Error codes are the NW_E_* of include/crispr_nw.h.
+ */
+#ifndef CRISPR_REGIONS_H
+#define CRISPR_REGIONS_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct nwr_ctx nwr_ctx;
+typedef struct nwr_bam nwr_bam;
+
+#define NWR_MAX_REGIONS (1 << 20)
+#define NWR_BY_REFERENCE 1
+#define NWR_EQX_AS_MATCH 2
+
+typedef struct nwr_region {
+    int64_t bpstart, bpend; /* 1-based, as in SAM text and the reference's region file */
+    int32_t ref_id;         /* index into the BAM's references; no record is on any other value */
+    int32_t reserved;
+} nwr_region;
+
+typedef struct nwr_result {
+    int64_t n_regions; /* the call's regions (NWR_BY_REFERENCE: the BAM's references) */
+    int64_t n_hits;
+    int64_t n_bytes;   /* bytes of text (and of quals) */
+    int64_t n_no_seq;  /* hits dropped because their record has no sequence or no qualities */
+    float kernel_ms;   /* device time of the call's kernels */
+    float upload_ms;   /* host wall time in the chunks' uploads */
+    void* handle;
+} nwr_result;
+
+/* Reads a BAM from `path`, or from the mem_len bytes at `mem` when path is NULL: BGZF (the blocks
+ * inflated in parallel on the host's thread pool, each block's CRC-32 and size checked; the
+ * empty EOF block is optional) or an already uncompressed BAM stream.  The header is parsed and
+ * every record is validated: block_size >= 32 + l_read_name + 4 n_cigar_op + (l_seq + 1) / 2 +
+ * l_seq, the record ends inside the stream, -1 <= ref_id < n_ref.  Anything else (bad magic, a
+ * truncated block, a CRC or size mismatch, a record past the end) is NW_E_INVALID with a message
+ * in err (err_cap bytes, may be NULL); an unreadable path is NW_E_STATE.  Uses no GPU. */
+int nwr_read_bam(const char* path, const uint8_t* mem, int64_t mem_len, nwr_bam** out, char* err, int64_t err_cap);
+void nwr_bam_free(nwr_bam* b);
+int64_t nwr_bam_count(const nwr_bam* b);
+/* The uncompressed stream; record i is the bytes [offsets[i], offsets[i + 1]) of it, from its
+ * block_size field on (offsets: int64 [count + 1]). */
+const uint8_t* nwr_bam_data(const nwr_bam* b, int64_t* nbytes);
+const int64_t* nwr_bam_offsets(const nwr_bam* b);
+int32_t nwr_bam_n_ref(const nwr_bam* b);
+/* The reference names, each ended by a NUL, one after the other; their lengths. */
+const char* nwr_bam_ref_names(const nwr_bam* b, int64_t* nbytes);
+const int32_t* nwr_bam_ref_lens(const nwr_bam* b);
+const char* nwr_bam_text(const nwr_bam* b, int64_t* nbytes);
+
+/* CRISPR_NWR_CHUNK=<records> is read here: records per chunk (default: chunks of about 256 MiB
+ * of records), so that tests reach the chunk edges on small inputs. */
+int nwr_create(int device, nwr_ctx** out);
+void nwr_destroy(nwr_ctx* c);
+const char* nwr_last_error(const nwr_ctx* c);
+
+/* The reads of every region (n_regions <= NWR_MAX_REGIONS, any order; ignored with
+ * NWR_BY_REFERENCE) from the records of `bam` (only a validated nwr_bam is ever uploaded).
+ * flags: NWR_BY_REFERENCE, NWR_EQX_AS_MATCH.  The BAM is processed in chunks of whole records;
+ * a chunk whose output reaches 2^32 bytes or 2^30 hits, or more regions than NWR_MAX_REGIONS,
+ * is NW_E_UNSUPPORTED.  Fills *res; the result stays with res->handle until nwr_release.  Zero
+ * records or zero regions give an empty result without touching the GPU.  Synchronous. */
+int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64_t n_regions, int32_t flags,
+                nwr_result* res);
+
+/* Copies the result into the caller's arrays (any may be NULL): region_offsets int64
+ * [n_regions + 1], the hits of region g (the caller's order) are [region_offsets[g],
+ * region_offsets[g + 1]); per hit src int64 (the record's index in the BAM), st / en int32 (the
+ * query indices before the cut to l_seq, saturated at 2^31 - 1); text_offsets int64 [n_hits + 1]
+ * into text and quals (n_bytes each). */
+int nwr_fetch(const nwr_result* res, int64_t* region_offsets, int64_t* src, int32_t* st, int32_t* en,
+              int64_t* text_offsets, uint8_t* text, uint8_t* quals);
+void nwr_release(nwr_result* res);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
