@@ -86,7 +86,11 @@ FLASH_EXPORTS = ("nwf_merge_batch", "nwf_last_error")
 TRIM_EXPORTS = ("nwt_trim_batch", "nwt_trim_program", "nwt_last_error")
 
 # Every symbol include/crispr_front.h declares.
-FRONT_EXPORTS = ("nwp_prepare", "nwp_fetch", "nwp_release", "nwp_last_error")
+FRONT_EXPORTS = ("nwp_prepare", "nwp_prepare_records", "nwp_fetch", "nwp_release", "nwp_last_error")
+
+# Every symbol include/crispr_ingest.h declares.
+INGEST_EXPORTS = ("nwi_parse_text", "nwi_parse_file", "nwi_info", "nwi_fetch", "nwi_release", "nwi_last_error")
+NWI_BAD_HEADER, NWI_BAD_PLUS, NWI_LEN_MISMATCH, NWI_BAD_QUAL = 1, 2, 4, 8
 
 # Every symbol include/crispr_synth.h declares (bench / test input generator).
 SYNTH_EXPORTS = ("nw_synth_offsets", "nw_synth_reads")
@@ -123,6 +127,14 @@ class NwpResult(ctypes.Structure):
     """nwp_result (include/crispr_front.h)."""
     _fields_ = [("n", c_int64), ("m", c_int64), ("total", c_int64), ("n_exc", c_int64), ("counts", c_int64 * 5),
                 ("trim", c_int64 * 4), ("kernel_ms", c_float * 5), ("handle", c_void_p)]
+
+
+class NwiSummary(ctypes.Structure):
+    """nwi_summary (include/crispr_ingest.h)."""
+    _fields_ = [("n", c_int64), ("lines", c_int64), ("trailing_lines", c_int64), ("lmax", c_int64),
+                ("flagged", c_int64 * 4), ("first_bad", c_int64), ("seq_bytes", c_int64), ("qual_bytes", c_int64),
+                ("name_bytes", c_int64), ("text_bytes", c_int64), ("upload_ms", c_float), ("kernel_ms", c_float),
+                ("inflate_ms", c_float)]
 
 
 class NwrRegion(ctypes.Structure):
@@ -265,7 +277,14 @@ def load() -> ctypes.CDLL:
                              + [c_int64] + [c_void_p] * 4 + [POINTER(c_float)]),
         "nwt_last_error": (c_char_p, []),
         "nwp_prepare": (c_int, [ctx_p, POINTER(NwpParams)] + [c_void_p] * 6 + [c_int64, POINTER(NwpResult)]),
+        "nwp_prepare_records": (c_int, [ctx_p, POINTER(NwpParams), c_void_p, c_void_p, POINTER(NwpResult)]),
         "nwp_fetch": (c_int, [POINTER(NwpResult)] + [c_void_p] * 9),
+        "nwi_parse_text": (c_int, [c_int, c_void_p, c_int64, POINTER(c_void_p)]),
+        "nwi_parse_file": (c_int, [c_int, c_char_p, POINTER(c_void_p)]),
+        "nwi_info": (c_int, [c_void_p, POINTER(NwiSummary)]),
+        "nwi_fetch": (c_int, [c_void_p] * 8),
+        "nwi_release": (None, [c_void_p]),
+        "nwi_last_error": (c_char_p, []),
         "nwp_release": (None, [POINTER(NwpResult)]),
         "nwp_last_error": (c_char_p, []),
         "nwq_create": (c_int, [c_int, POINTER(c_void_p)]),
@@ -363,7 +382,7 @@ def exported_symbols() -> dict:
     """Map of each declared symbol to whether the loaded library exports it."""
     lib = load()
     out = {}
-    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + COUNT_EXPORTS + REGION_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + SYNTH_EXPORTS:
+    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + COUNT_EXPORTS + REGION_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + INGEST_EXPORTS + SYNTH_EXPORTS:
         try:
             getattr(lib, name)
             out[name] = name not in _MISSING

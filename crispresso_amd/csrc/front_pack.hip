@@ -6,6 +6,9 @@
 // device: the surviving reads' text made dense, their offsets / lengths / group offsets, the
 // 2-bit stream and the exception list.  The context then takes the batch with device-to-device
 // copies on its own stream behind an event (nw_front::set_packed_batch, nw_host.cpp).
+// nwp_prepare_records is the same call on records the FASTQ ingest (fastq_parse.hip) left in HBM:
+// nothing is uploaded, the kernels read the ingest's streams and offsets where they lie, and the
+// ingest's flags and longest read stand in for the host's checks of the reads.
 //
 // The packer is block sums / one scan block / scatter, three launches with nothing handed between
 // blocks inside a launch (no wait anywhere):
@@ -37,6 +40,7 @@
 #include "../../include/crispr_front.h"
 #include "flash_device.h"
 #include "front_device.h"
+#include "ingest_device.h"
 #include "nw_device.h"
 #include "trim_device.h"
 
@@ -385,54 +389,55 @@ extern "C" int nwp_fetch(const nwp_result* res, uint8_t* status, int64_t* offset
     return 0;
 }
 
-extern "C" int nwp_prepare(nw_ctx* ctx, const nwp_params* params, const uint8_t* seq1, const uint8_t* qual1,
-                           const int64_t* off1, const uint8_t* seq2, const uint8_t* qual2, const int64_t* off2,
-                           int64_t n, nwp_result* out) {
-    using namespace nwp;
-    const char* who = "nwp_prepare";
-    const bool paired = seq2 != nullptr;
+namespace nwp {
+
+// What both entries check before they look at the reads: the arguments, the context's state, the
+// trim program.  reads_ok: the entry's own reads are all there.  On 0, *out holds an empty handle
+// (all a call with n == 0 returns).
+int begin_call(const char* who, nw_ctx* ctx, const nwp_params* params, bool paired, bool reads_ok, int64_t n,
+               nwp_result* out, nwt::Program& P) {
+    const std::string me = std::string(who) + ": ";
     if (!ctx || !params || !out || n < 0 || params->n_steps < 0 || (params->n_steps > 0 && !params->steps))
-        return fail(-1, "nwp_prepare: null argument or negative count");
+        return fail(-1, me + "null argument or negative count");
     memset(out, 0, sizeof(*out));
     int rc = nw_front::check_state(ctx);
-    if (rc != NW_OK) return fail(rc, std::string("nwp_prepare: ") + nw_last_error(ctx));
+    if (rc != NW_OK) return fail(rc, me + nw_last_error(ctx));
     if (params->clip) {
         rc = nwt::check_counts(who, params->adapters, params->adapter_off, params->adapter_role, params->n_adapters,
                                params->prefixes, params->prefix_off, params->n_prefix_pairs);
         if (rc != 0) return fail_trim(rc);
     }
-    if (n > 0 && (!seq1 || !qual1 || !off1 || (paired && (!qual2 || !off2))))
-        return fail(-1, "nwp_prepare: null argument");
+    if (!reads_ok) return fail(-1, me + "null argument");
     if (paired && (params->flash.min_overlap < 1 || params->flash.max_overlap < 1))
-        return fail(-1, "nwp_prepare: min_overlap and max_overlap must be >= 1");
-    nwt::Program P;
+        return fail(-1, me + "min_overlap and max_overlap must be >= 1");
     rc = nwt::program_check(who, params->clip, params->adapters, params->adapter_off, params->adapter_role,
                             params->n_adapters, params->prefixes, params->prefix_off, params->n_prefix_pairs,
                             params->steps, params->n_steps, P);
     if (rc != 0) return fail_trim(rc);
-    const bool trim = P.clip || P.sa.n_steps > 0;
-    const bool filter = params->min_avg_quality > 0 || params->min_single_quality > 0;
     out->n = n;
     Handle* h = new Handle;
     h->device = nw_front::device_of(ctx);
     h->offsets.assign(1, 0);
     out->handle = h;
-    if (n == 0) return 0;
+    return 0;
+}
+
+// Everything after the reads are on the device: the batch of out's handle has s1 .. o2 (its own
+// upload, or the ingest's arrays) and its events (Batch::begin); n > 0, t1 and t2 are the mates'
+// bytes, lmax the longest read.  Filter, trim, merge, pack, and the context's adoption.
+int run_call(const char* who, nw_ctx* ctx, const nwp_params* params, nwt::Program& P, bool paired, int64_t n, int lmax,
+             int64_t t1, int64_t t2, nwp_result* out) {
+    const std::string me = std::string(who) + ": ";
+    Handle* h = (Handle*)out->handle;
+    nwt::Batch& b = h->b;
+    const bool trim = P.clip || P.sa.n_steps > 0;
+    const bool filter = params->min_avg_quality > 0 || params->min_single_quality > 0;
     auto bail = [&](int code) {
         nwp_release(out);
         return code;
     };
-    int lmax = 0;
-    rc = nwt::check_reads(who, qual1, off1, qual2, off2, n, paired, &lmax);
-    if (rc != 0) return bail(fail_trim(rc));
-    const int64_t t1 = off1[n], t2 = paired ? off2[n] : 0;
-    if ((uint64_t)t1 + (uint64_t)t2 >= (1ull << 32))
-        return bail(fail(-3, "nwp_prepare: 2^32 or more bytes of reads in one call are not supported"));
-
-    if (hipSetDevice(h->device) != hipSuccess) return bail(fail(-4, "nwp_prepare: hipSetDevice failed"));
-    nwt::Batch& b = h->b;
     const int64_t blocks = (n + kBlk - 1) / kBlk;
-    bool have = b.alloc_reads(t1, t2, n);
+    bool have = true;
     int32_t* d_win[4] = {nullptr, nullptr, nullptr, nullptr};   // start1, keep1, start2, keep2
     if (trim) have = nwt::program_alloc(b, P, n, d_win) && have;
     uint8_t* d_live = filter ? (uint8_t*)b.dev((size_t)n) : nullptr;
@@ -453,12 +458,11 @@ extern "C" int nwp_prepare(nw_ctx* ctx, const nwp_params* params, const uint8_t*
     pa.totals = (int64_t*)b.dev(sizeof(int64_t) * 3);
     pa.blocks = blocks;
     if (!have || (filter && !d_live) || !pa.status || !pa.nexc || !pa.sums || !pa.counters || !pa.totals)
-        return bail(fail(-4, "nwp_prepare: hipMalloc failed"));
+        return bail(fail(-4, me + "hipMalloc failed"));
 
     auto hip_fail = [&]() {
-        return bail(fail(-4, std::string("nwp_prepare: HIP error: ") + hipGetErrorString(hipGetLastError())));
+        return bail(fail(-4, me + "HIP error: " + hipGetErrorString(hipGetLastError())));
     };
-    if (!b.upload(h->device, seq1, qual1, off1, seq2, qual2, off2, n, paired)) return hip_fail();
     float* ms = out->kernel_ms;
     if (filter) {
         FilterArgs fa{};
@@ -524,7 +528,7 @@ extern "C" int nwp_prepare(nw_ctx* ctx, const nwp_params* params, const uint8_t*
     pa.words = h->words = (uint32_t*)b.dev(sizeof(uint32_t) * std::max<int64_t>(nwords, 1) + 64);
     if (!pa.offsets || !pa.lens || !pa.src || !pa.gbase || !pa.text || (params->want_quals && !pa.quals) ||
         !pa.exc_pos || !pa.exc_byte || !pa.words)
-        return bail(fail(-4, "nwp_prepare: hipMalloc failed"));
+        return bail(fail(-4, me + "hipMalloc failed"));
     if (hipEventRecord(b.e0, nullptr) != hipSuccess) return hip_fail();
     hipLaunchKernelGGL(nwp_scatter_kernel, dim3((unsigned)blocks), dim3(kBlk), 0, nullptr, pa);
     if (nwords > 0)
@@ -537,7 +541,93 @@ extern "C" int nwp_prepare(nw_ctx* ctx, const nwp_params* params, const uint8_t*
         hipMemcpy(h->lens.data(), pa.lens, sizeof(uint16_t) * m, hipMemcpyDeviceToHost) != hipSuccess)
         return hip_fail();
     const nw_front::PackedSrc src{(const uint8_t*)pa.words, pa.lens, pa.gbase, pa.exc_pos, pa.exc_byte, true, b.e1};
-    rc = nw_front::set_packed_batch(ctx, src, h->offsets.data(), h->lens.data(), m, n_exc);
-    if (rc != NW_OK) return bail(fail(rc, std::string("nwp_prepare: ") + nw_last_error(ctx)));
+    const int rc = nw_front::set_packed_batch(ctx, src, h->offsets.data(), h->lens.data(), m, n_exc);
+    if (rc != NW_OK) return bail(fail(rc, me + nw_last_error(ctx)));
     return 0;
+}
+
+}  // namespace nwp
+
+extern "C" int nwp_prepare(nw_ctx* ctx, const nwp_params* params, const uint8_t* seq1, const uint8_t* qual1,
+                           const int64_t* off1, const uint8_t* seq2, const uint8_t* qual2, const int64_t* off2,
+                           int64_t n, nwp_result* out) {
+    using namespace nwp;
+    const char* who = "nwp_prepare";
+    const bool paired = seq2 != nullptr;
+    nwt::Program P;
+    const bool reads_ok = !(n > 0 && (!seq1 || !qual1 || !off1 || (paired && (!qual2 || !off2))));
+    int rc = begin_call(who, ctx, params, paired, reads_ok, n, out, P);
+    if (rc != 0 || n == 0) return rc;
+    auto bail = [&](int code) {
+        nwp_release(out);
+        return code;
+    };
+    int lmax = 0;
+    rc = nwt::check_reads(who, qual1, off1, qual2, off2, n, paired, &lmax);
+    if (rc != 0) return bail(fail_trim(rc));
+    const int64_t t1 = off1[n], t2 = paired ? off2[n] : 0;
+    if ((uint64_t)t1 + (uint64_t)t2 >= (1ull << 32))
+        return bail(fail(-3, "nwp_prepare: 2^32 or more bytes of reads in one call are not supported"));
+    Handle* h = (Handle*)out->handle;
+    if (hipSetDevice(h->device) != hipSuccess) return bail(fail(-4, "nwp_prepare: hipSetDevice failed"));
+    if (!h->b.alloc_reads(t1, t2, n)) return bail(fail(-4, "nwp_prepare: hipMalloc failed"));
+    if (!h->b.upload(h->device, seq1, qual1, off1, seq2, qual2, off2, n, paired))
+        return bail(fail(-4, std::string("nwp_prepare: HIP error: ") + hipGetErrorString(hipGetLastError())));
+    return run_call(who, ctx, params, P, paired, n, lmax, t1, t2, out);
+}
+
+extern "C" int nwp_prepare_records(nw_ctx* ctx, const nwp_params* params, const nwi_records* r1, const nwi_records* r2,
+                                   nwp_result* out) {
+    using namespace nwp;
+    const char* who = "nwp_prepare_records";
+    const bool paired = r2 != nullptr;
+    const int64_t n = !r1 ? 0 : paired ? std::min(r1->info.n, r2->info.n) : r1->info.n;
+    nwt::Program P;
+    int rc = begin_call(who, ctx, params, paired, r1 != nullptr, n, out, P);
+    if (rc != 0 || n == 0) return rc;
+    auto bail = [&](int code) {
+        nwp_release(out);
+        return code;
+    };
+    Handle* h = (Handle*)out->handle;
+    const nwi_records* mates[2] = {r1, r2};
+    for (int k = 0; k < (paired ? 2 : 1); ++k)
+        if (mates[k]->device != h->device)
+            return bail(fail(-1, "nwp_prepare_records: the records lie on another device than the context"));
+    if (hipSetDevice(h->device) != hipSuccess) return bail(fail(-4, "nwp_prepare_records: hipSetDevice failed"));
+    auto hip_fail = [&]() {
+        return bail(fail(-4, std::string("nwp_prepare_records: HIP error: ") + hipGetErrorString(hipGetLastError())));
+    };
+    // the two refusals nwt::check_reads makes on host arrays, from the ingest's own results
+    int64_t t[2] = {0, 0};
+    int64_t lmax = 0;
+    for (int k = 0; k < (paired ? 2 : 1); ++k) {
+        const nwi_records* r = mates[k];
+        const int64_t bad = r->info.first_bad;
+        if (bad >= 0 && bad < n) {   // first_bad is the smallest flagged index: none below it
+            uint8_t f = 0;
+            if (hipMemcpy(&f, r->flags + bad, 1, hipMemcpyDeviceToHost) != hipSuccess) return hip_fail();
+            return bail(fail(-1, std::string("nwp_prepare_records: record ") + std::to_string(bad) + " of R" +
+                                     std::to_string(k + 1) + ": " + nwi::flag_reason(f)));
+        }
+        lmax = std::max(lmax, r->info.lmax);
+        // no flag among the first n: their base and quality offsets are equal
+        if (hipMemcpy(&t[k], r->off[0] + n, sizeof(int64_t), hipMemcpyDeviceToHost) != hipSuccess) return hip_fail();
+    }
+    if (lmax > 4096)
+        return bail(fail(-3, "nwp_prepare_records: a read longer than 4096 bases (" + std::to_string(lmax) +
+                                 ") is not supported"));
+    if ((uint64_t)t[0] + (uint64_t)t[1] >= (1ull << 32))
+        return bail(fail(-3, "nwp_prepare_records: 2^32 or more bytes of reads in one call are not supported"));
+    // the batch reads the records where the ingest left them (nothing copied; the kernels only read)
+    nwt::Batch& b = h->b;
+    b.s1 = r1->stream[0], b.q1 = r1->stream[1], b.o1 = r1->off[0];
+    if (paired) {
+        b.s2 = r2->stream[0], b.q2 = r2->stream[1], b.o2 = r2->off[0];
+    } else {   // as alloc_reads leaves them
+        b.s2 = (uint8_t*)b.dev(8), b.q2 = (uint8_t*)b.dev(8), b.o2 = (int64_t*)b.dev(sizeof(int64_t));
+        if (!b.s2 || !b.q2 || !b.o2) return bail(fail(-4, "nwp_prepare_records: hipMalloc failed"));
+    }
+    if (!b.begin(h->device)) return hip_fail();
+    return run_call(who, ctx, params, P, paired, n, (int)lmax, t[0], t[1], out);
 }

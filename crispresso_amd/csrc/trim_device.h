@@ -76,7 +76,11 @@ struct Batch {
             ok = hipMemcpy(s2, seq2, t2, hipMemcpyHostToDevice) == hipSuccess &&
                  hipMemcpy(q2, qual2, t2, hipMemcpyHostToDevice) == hipSuccess &&
                  hipMemcpy(o2, off2, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess;
-        ok = ok && hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+        return ok && begin(device);
+    }
+    // the events and the launch cap: what a call needs once its reads are on the device
+    bool begin(int device) {
+        const bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
         hipDeviceProp_t prop;
         if (ok && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
             cus = prop.multiProcessorCount;

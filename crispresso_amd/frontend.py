@@ -9,7 +9,10 @@ with the clip, steps and merge kernels of :mod:`crispresso_amd.trim` and
 ``aligner.upload_packed(pack_2bit(text))`` would have left them, and the aligner's
 ``run_async`` / ``sync`` / ``download_ops`` / ``device_ops`` then run with nothing uploaded in
 between.  The host receives each input read's status, the batch's text, offsets, lengths and
-source indices.  There is no CPU fallback: without the library or a GPU every call raises
+source indices.  :func:`prepare_fastq` is that call on FASTQ files read by the interpreter;
+:func:`prepare_fastq_device` parses the files on the GPU (:mod:`crispresso_amd.ingest`) and hands
+the records to the same kernels where they lie (``nwp_prepare_records``).  There is no CPU
+fallback: without the library or a GPU every call raises
 :class:`crispresso_amd._lib.NativeLibraryError`.
 """
 from __future__ import annotations
@@ -24,6 +27,7 @@ from . import _lib
 from .aligner import GpuAligner, PackedReads
 from .fastq import fasta_name
 from .flash import FlashOptions, _pack, read_fastq
+from .ingest import read_fastq_records
 from .trim import MAX_STEPS, TrimError, TrimProgram, UnsupportedTrimStep, _check_packed, _clip_arguments
 
 FILTERED, TRIMMED, NOT_COMBINED, COMBINED, COMBINED_OUTIE = (
@@ -75,32 +79,13 @@ def prepare_packed(aligner: GpuAligner, s1: np.ndarray, q1: np.ndarray, off1: np
     context in rows mode is refused, as by ``upload_packed``'s C entry).  When no read survives the
     context keeps its previous batch."""
     paired = s2 is not None
-    prog = trim if isinstance(trim, TrimProgram) else (TrimProgram.from_steps(trim) if trim else TrimProgram())
-    if prog.clip is not None and prog.clip.minlen != 0:
-        raise TrimError("prepare_packed: the clip options' minlen must be 0 (MINLEN is a step)")
-    if len(prog.steps) > MAX_STEPS:
-        raise UnsupportedTrimStep(f"more than {MAX_STEPS} steps after ILLUMINACLIP")
+    prog = _program("prepare_packed", trim)
     s1, q1, off1, s2, q2, off2 = _check_packed("prepare_packed", s1, q1, off1, s2, q2, off2)
     n = len(off1) - 1
     filt = min_bp_quality > 0 or min_single_bp_quality > 0
     if filt and n and (np.any(np.diff(off1) == 0) or (paired and np.any(np.diff(off2) == 0))):
         raise ValueError("prepare_packed: a record has no qualities")   # numpy: min() of an empty array
-    o = flash or FlashOptions()
-    p = _lib.NwpParams()
-    p.min_avg_quality, p.min_single_quality = int(min_bp_quality), int(min_single_bp_quality)
-    _alive = None
-    if prog.clip is not None:
-        _args, _alive = _clip_arguments(prog.clip, 0)   # _alive: the arrays the pointers point into
-        clip, ad, ad_off, roles, pre, pre_off = _alive
-        p.clip = ctypes.pointer(clip)
-        p.adapters, p.adapter_off, p.adapter_role = _lib.ptr(ad), _lib.ptr(ad_off), _lib.ptr(roles)
-        p.prefixes, p.prefix_off = _lib.ptr(pre), _lib.ptr(pre_off)
-        p.n_adapters, p.n_prefix_pairs = len(prog.clip.adapters), len(prog.clip.prefix_pairs)
-    steps = prog.native_steps()
-    p.steps, p.n_steps = ctypes.cast(steps, ctypes.POINTER(_lib.NwtStep)), len(prog.steps)
-    p.flash = _lib.NwfParams(o.min_overlap, o.max_overlap, o.max_mismatch_density, int(o.allow_outies),
-                             o.phred_offset, int(o.cap_mismatch_quals))
-    p.want_quals = int(with_quals)
+    p, _alive = _params(prog, min_bp_quality, min_single_bp_quality, flash, with_quals)
     lib = _lib.load()
     if force_ops_output:
         aligner.set_output("ops")
@@ -110,6 +95,44 @@ def prepare_packed(aligner: GpuAligner, s1: np.ndarray, q1: np.ndarray, off1: np
                          _lib.ptr(off2) if paired else None, n, ctypes.byref(res))
     if rc != 0:
         raise FrontError(lib.nwp_last_error().decode(errors="replace"), rc)
+    return _collect(aligner, lib, res, n, with_quals, with_packed)
+
+
+def _program(who: str, trim) -> TrimProgram:
+    prog = trim if isinstance(trim, TrimProgram) else (TrimProgram.from_steps(trim) if trim else TrimProgram())
+    if prog.clip is not None and prog.clip.minlen != 0:
+        raise TrimError(f"{who}: the clip options' minlen must be 0 (MINLEN is a step)")
+    if len(prog.steps) > MAX_STEPS:
+        raise UnsupportedTrimStep(f"more than {MAX_STEPS} steps after ILLUMINACLIP")
+    return prog
+
+
+def _params(prog: TrimProgram, min_bp_quality: int, min_single_bp_quality: int, flash: Optional[FlashOptions],
+            with_quals: bool):
+    """nwp_params and the arrays its pointers point into (to be kept until the call returns)."""
+    o = flash or FlashOptions()
+    p = _lib.NwpParams()
+    p.min_avg_quality, p.min_single_quality = int(min_bp_quality), int(min_single_bp_quality)
+    alive = []
+    if prog.clip is not None:
+        _args, arrays = _clip_arguments(prog.clip, 0)
+        clip, ad, ad_off, roles, pre, pre_off = arrays
+        alive.append(arrays)
+        p.clip = ctypes.pointer(clip)
+        p.adapters, p.adapter_off, p.adapter_role = _lib.ptr(ad), _lib.ptr(ad_off), _lib.ptr(roles)
+        p.prefixes, p.prefix_off = _lib.ptr(pre), _lib.ptr(pre_off)
+        p.n_adapters, p.n_prefix_pairs = len(prog.clip.adapters), len(prog.clip.prefix_pairs)
+    steps = prog.native_steps()
+    alive.append(steps)
+    p.steps, p.n_steps = ctypes.cast(steps, ctypes.POINTER(_lib.NwtStep)), len(prog.steps)
+    p.flash = _lib.NwfParams(o.min_overlap, o.max_overlap, o.max_mismatch_density, int(o.allow_outies),
+                             o.phred_offset, int(o.cap_mismatch_quals))
+    p.want_quals = int(with_quals)
+    return p, alive
+
+
+def _collect(aligner: GpuAligner, lib, res, n: int, with_quals: bool, with_packed: bool) -> PreparedBatch:
+    """The host's copies of a successful nwp_prepare / nwp_prepare_records; releases ``res``."""
     try:
         m, total, n_exc = int(res.m), int(res.total), int(res.n_exc)
         pool = _lib.pinned_pool()
@@ -175,6 +198,53 @@ def prepare_fastq(aligner: GpuAligner, r1: str, r2: Optional[str] = None, **kw) 
     names = []
     for i in pb.src:
         h = n1[int(i)]
+        if r2 is not None and h.endswith(b"/1"):
+            h = h[:-2]
+        names.append(fasta_name(b"@" + h))
+    return pb, names
+
+
+def prepare_fastq_device(aligner: GpuAligner, r1: str, r2: Optional[str] = None, *, min_bp_quality: int = 0,
+                         min_single_bp_quality: int = 0, trim: Union[None, str, List[str], TrimProgram] = None,
+                         flash: Optional[FlashOptions] = None, with_quals: bool = False, with_packed: bool = False,
+                         force_ops_output: bool = True) -> Tuple[PreparedBatch, List[str]]:
+    """:func:`prepare_fastq` with the files parsed on the GPU (:mod:`crispresso_amd.ingest`,
+    ``nwi_parse_file``) and handed to the front end where they lie (``nwp_prepare_records``): the
+    same arguments, the same ``(PreparedBatch, names)``; only the text of each file is uploaded,
+    and only R1's names come back.  A malformed record among the first ``min(n1, n2)`` (header,
+    '+' line, line lengths, quality range) refuses the call with :class:`FrontError` (code -1),
+    a sequence longer than 4096 bases anywhere in either file with code -3."""
+    prog = _program("prepare_fastq_device", trim)
+    lib = _lib.load()
+    a = read_fastq_records(r1, aligner.device, strict=False, fetch=False)
+    b = None
+    try:
+        if r2 is not None:
+            b = read_fastq_records(r2, aligner.device, strict=False, fetch=False)
+        n = len(a) if b is None else min(len(a), len(b))
+        filt = min_bp_quality > 0 or min_single_bp_quality > 0
+        if filt and n:   # as prepare_packed: the filter's mean of an empty read (a flagged record: refused below)
+            for rec in (a, b):
+                if rec is not None and not 0 <= rec.info["first_bad"] < n and np.any(np.diff(rec.fetch_offsets()[:n + 1]) == 0):
+                    raise ValueError("prepare_fastq_device: a record has no qualities")
+        p, _alive = _params(prog, min_bp_quality, min_single_bp_quality, flash, with_quals)
+        if force_ops_output:
+            aligner.set_output("ops")
+        res = _lib.NwpResult()
+        rc = lib.nwp_prepare_records(aligner._h, ctypes.byref(p), a._h, b._h if b is not None else None,
+                                     ctypes.byref(res))
+        if rc != 0:
+            raise FrontError(lib.nwp_last_error().decode(errors="replace"), rc)
+        pb = _collect(aligner, lib, res, n, with_quals, with_packed)
+        raw, name_off = a.fetch_names()
+        raw, name_off = raw.tobytes(), name_off.tolist()
+    finally:
+        a.close()
+        if b is not None:
+            b.close()
+    names = []
+    for i in pb.src.tolist():
+        h = raw[name_off[i]:name_off[i + 1]]
         if r2 is not None and h.endswith(b"/1"):
             h = h[:-2]
         names.append(fasta_name(b"@" + h))

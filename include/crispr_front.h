@@ -6,7 +6,8 @@
  * the clip and steps kernels of crispr_trim.h, the merge kernel of crispr_flash.h on the trimmed
  * windows, and a device packer that leaves the surviving reads in HBM as nw_pack_reads +
  * nw_batch_upload_packed (crispr_nw.h) would have: the context then runs nw_batch_run_async,
- * nw_batch_download_ops, nw_batch_device_ops with nothing uploaded in between.
+ * nw_batch_download_ops, nw_batch_device_ops with nothing uploaded in between.  nwp_prepare_records
+ * is the same call on records the FASTQ ingest (crispr_ingest.h) already left in HBM.
  *
  * The binding is crispresso_amd/frontend.py (ctypes).
  */
@@ -16,6 +17,7 @@
 #include <stdint.h>
 
 #include "crispr_flash.h"
+#include "crispr_ingest.h"
 #include "crispr_nw.h"
 #include "crispr_trim.h"
 
@@ -79,6 +81,17 @@ typedef struct nwp_result {
  * describes it (the context's nw_last_error for an error of the adoption). */
 int nwp_prepare(nw_ctx* ctx, const nwp_params* params, const uint8_t* seq1, const uint8_t* qual1, const int64_t* off1,
                 const uint8_t* seq2, const uint8_t* qual2, const int64_t* off2, int64_t n, nwp_result* out);
+
+/* nwp_prepare on records the FASTQ ingest left on the context's device (crispr_ingest.h), with
+ * nothing uploaded: the first n records of r1 (r2 == NULL: single-end), or the first
+ * n = min(n1, n2) of each mate.  The records are only read, and only during the call.
+ *
+ * The ingest's results stand in for nwp_prepare's checks of the reads: -1 when a flag is set among
+ * the records the call would use (the message names the first flagged record, its mate and the
+ * reason), -3 when the longest sequence of either file exceeds 4096 bases.  Everything else is as
+ * nwp_prepare. */
+int nwp_prepare_records(nw_ctx* ctx, const nwp_params* params, const nwi_records* r1, const nwi_records* r2,
+                        nwp_result* out);
 
 /* Copies of the result into caller-owned host arrays; any pointer may be NULL.  status [n];
  * offsets [m + 1] from 0; lens [m]; src [m]: the input index of each batch read; text [total];
