@@ -462,11 +462,53 @@ __device__ __forceinline__ bool cert_indel(const KernelArgs& a, const unsigned* 
     return ok;
 }
 
+// (write_read_bytes) the dword v of batch positions p .. p + 3 into the bytes of the read [o, e) among them
+__device__ __forceinline__ void store_read_dword(uint8_t* dst, long long p, long long o, long long e, unsigned v) {
+    if (p >= o && p + 4 <= e) {
+        *(unsigned*)(dst + p) = v;
+    } else {
+        for (int b = 0; b < 4; ++b)
+            if (p + b >= o && p + b < e) dst[p + b] = (uint8_t)(v >> (8 * b));
+    }
+}
+
 // Packed input: the bytes of the reads in dp (the lanes' reads at my_off, my_len; the whole wavefront)
-// decoded into a.reads -- each read's own bytes exactly (neighbouring reads' bytes are never written by
-// another read's wavefront: no races between blocks)
-__device__ __forceinline__ void write_read_bytes(const KernelArgs& a, unsigned long long dp, long long my_off, int my_len) {
+// decoded into a.reads -- each read's own bytes exactly, and every byte stored once, as its final value:
+// the reads in excm hold exception bytes (the block's slice [x0, x1) of the call's list), which replace
+// the decoded 'A' of their places in registers, before the store.
+// Within one pass a read's bytes are written by its own wavefront only (neighbouring reads' bytes are
+// never touched: no races between blocks or chunks of the pass).  Across the two passes of a dual call
+// (both decode the same reads into the same buffer, on concurrent streams) the rule is DESIGN.md 4c's:
+// while a kernel of one pass may read a byte, the other pass stores nothing but that byte's final value
+// to it -- which holds because no store here ever carries a provisional byte.
+__device__ __forceinline__ void write_read_bytes(const KernelArgs& a, unsigned long long dp, long long my_off, int my_len,
+                                                 unsigned long long excm = 0ull, long long x0 = 0, long long x1 = 0) {
     const int lane = threadIdx.x & 63;
+    // the reads holding exceptions (rare): one at a time, each dword patched from the exception list
+    for (unsigned long long de = dp & excm; de; de &= de - 1) {
+        const int u = (int)__builtin_ctzll(de);
+        const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)my_off, u);
+        const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(my_off >> 32), u);
+        const long long o = (long long)(((unsigned long long)hi << 32) | lo);
+        const long long e = o + __builtin_amdgcn_readlane(my_len, u);
+        for (long long p = (o & ~3ll) + 4 * lane; p < e; p += 256) {
+            unsigned v = pk_decode4_al(a, p);
+            long long t = x0, th = x1;   // the first exception at or after p
+            while (t < th) {
+                const long long mid = (t + th) >> 1;
+                if (a.pk_exc_pos[mid] < p) t = mid + 1;
+                else th = mid;
+            }
+            for (; t < x1; ++t) {
+                const long long q = a.pk_exc_pos[t];
+                if (q >= p + 4) break;
+                const unsigned sh = 8u * (unsigned)(q - p);
+                v = (v & ~(0xffu << sh)) | ((unsigned)pk_exc_store_byte(a.pk_exc_byte[t]) << sh);
+            }
+            store_read_dword(const_cast<uint8_t*>(a.reads), p, o, e, v);
+        }
+    }
+    dp &= ~excm;
     // kWr reads at a time, lane l their dwords l, l + 64, ...: all their loads in flight
     // before any store (one read per round trip measured 2.7x the byte-input classify)
     constexpr int kWr = 8;
@@ -499,12 +541,7 @@ __device__ __forceinline__ void write_read_bytes(const KernelArgs& a, unsigned l
             for (int t = 0; t < kWr; ++t) {
                 const long long p = (o[t] & ~3ll) + 256 * rd2 + 4 * lane;
                 if (p >= e[t]) continue;
-                if (p >= o[t] && p + 4 <= e[t]) {
-                    *(unsigned*)(dst + p) = v[t];
-                } else {
-                    for (int b = 0; b < 4; ++b)
-                        if (p + b >= o[t] && p + b < e[t]) dst[p + b] = (uint8_t)(v[t] >> (8 * b));
-                }
+                store_read_dword(dst, p, o[t], e[t], v[t]);
             }
         }
     }
@@ -645,8 +682,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
     };
     auto ham16 = [&](unsigned x, unsigned y) { const unsigned z = x ^ y; return __builtin_popcount((z | (z >> 1)) & 0x55555555u); };
     // a wavefront batch of the 64 reads r0 .. r0 + 63 (below r_end): lane u holds read r0 + u's
-    // offset and length; exc: the reads holding an exception byte (packed input)
-    auto batch = [&](long long r0, long long r_end, long long my_off, int my_len, bool exc) {
+    // offset and length; exc: the reads holding an exception byte (packed input), their block's
+    // slice [x0, x1) of the call's exception list
+    auto batch = [&](long long r0, long long r_end, long long my_off, int my_len, bool exc, long long x0, long long x1) {
         const long long r = r0 + lane;
         unsigned long long cand = __ballot(my_len == La && !exc);   // reads of the amplicon's length
         unsigned long long exact = 0ull, sub1 = 0ull, sub2 = 0ull;
@@ -1147,12 +1185,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
             }
         }
         // packed input: the bytes of every read that needs the DP (the only reads a later kernel
-        // reads), exactly its own bytes (neighbouring reads' bytes are never written by another
-        // read's wave: no races between blocks); exception bytes follow (below)
+        // reads), exactly its own bytes, each stored once as its final value, exception bytes included
+        // (write_read_bytes: within a pass no other wave writes them; the other pass of a dual call
+        // stores the same values)
         if constexpr (PK)
             write_read_bytes(a, __ballot(r < r_end && my_len > 0 &&
                                          !(((exact | sub1 | sub2 | win | known | pend3 | pend_i) >> lane) & 1ull)),
-                             my_off, my_len);
+                             my_off, my_len, __ballot(exc), x0, x1);
         // deferred certificates (KernelArgs::cert_q): the wavefront's queued reads for nw_band_cert, the
         // three-substitution candidates from the front of its 64 entries, the one-indel ones from the back
         if constexpr (PK) {
@@ -1172,7 +1211,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
             const long long r = r0 + lane;
             const long long my_off = r < a.n ? a.offsets[r] : 0;
             const int my_len = r < a.n ? (int)(a.offsets[r + 1] - my_off) : -1;
-            batch(r0, a.n, my_off, my_len, false);
+            batch(r0, a.n, my_off, my_len, false, 0, 0);
         }
     } else {
         __shared__ long long s_off[kPkBlock + 1];
@@ -1246,17 +1285,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
             const long long r = r0 + lane;
             const long long my_off = r < bh ? s_off[r - bl] : 0;
             const int my_len = r < bh ? (int)(s_off[r - bl + 1] - my_off) : -1;
-            batch(r0, bh, my_off, my_len, r < bh && s_exc[r - bl] != 0);
+            batch(r0, bh, my_off, my_len, r < bh && s_exc[r - bl] != 0, x0, x1);
         } else if (a.cert_q && lane == 0) {
             a.cert_cnt[(long long)blockIdx.x * 4 + wave] = 0;   // (every wavefront's queue count is written)
         }
-        if (any_exc && x1 > x0) {
-            // after every wave's byte stores (completed: workgroup-scope release), the exception bytes
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-            __syncthreads();
-            uint8_t* dst = const_cast<uint8_t*>(a.reads);
-            for (long long t = x0 + tid; t < x1; t += blockDim.x) dst[a.pk_exc_pos[t]] = a.pk_exc_byte[t];
-        }
+        // (every exception byte is in a flagged read, flagged reads all need the DP, and their bytes went
+        // out with the exceptions in place: no store of a decoded 'A' that a later one would correct)
     }
 }
 

@@ -332,6 +332,9 @@ struct LenSeg {
     int64_t* d_off = nullptr;
 };
 constexpr int kLenGroup = 1024;
+// An exception byte as the byte buffer holds it: a letter in upper case, like the decoded A C T G
+// (every comparison the kernels make is case-insensitive; the buffer's readers get one form of a read)
+__host__ __device__ inline uint8_t pk_exc_store_byte(uint8_t b) { return b >= 'a' && b <= 'z' ? (uint8_t)(b - 32) : b; }
 hipError_t launch_unpack(const uint32_t* packed, int64_t pbyte0, int64_t b0, int64_t b1, const int64_t* exc_pos,
                          const uint8_t* exc_byte, int64_t e0, int64_t e1, uint8_t* dst, int64_t bias, hipStream_t s,
                          const LenSeg* lens = nullptr);

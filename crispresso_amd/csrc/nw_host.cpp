@@ -316,6 +316,7 @@ struct nw_ctx {
     int64_t ops_stride = 1;            // reads per slot row (the chunk capacity: ops_reserve)
     hipStream_t s_in = nullptr, s_out = nullptr;
     std::vector<hipEvent_t> ev_in, ev_cs, ev_ce, ev_out, ev_bulk;
+    std::vector<hipEvent_t> ev_up;    // a dual call's exact-kernel path: after chunk k's unpack (its twin waits for it)
     hipEvent_t ev_h0 = nullptr;
     hipEvent_t ev_start = nullptr;     // the second compute stream starts after the first's set-up
     int64_t* h_ctl = nullptr;          // pinned: per chunk ctl[0, kOpsCtl) copied back
@@ -883,7 +884,7 @@ void nw_destroy(nw_ctx* c) {
     for (int k = 1; k < kComputeStreams; ++k)
         if (c->cstream[k]) (void)hipStreamSynchronize(c->cstream[k]);
     if (c->s_out) (void)hipStreamSynchronize(c->s_out);
-    for (auto* v : {&c->ev_in, &c->ev_cs, &c->ev_ce, &c->ev_out})
+    for (auto* v : {&c->ev_in, &c->ev_cs, &c->ev_ce, &c->ev_out, &c->ev_up})
         for (hipEvent_t e : *v) (void)hipEventDestroy(e);
     if (c->h_ctl) (void)hipHostFree(c->h_ctl);
     if (c->h_lens) (void)hipHostFree(c->h_lens);
@@ -1487,6 +1488,7 @@ int ops_events(nw_ctx* c, size_t chunks) {
     HIP_OR_FAIL(c, grow(c->ev_ce, hipEventDefault));
     HIP_OR_FAIL(c, grow(c->ev_out, hipEventDisableTiming));
     HIP_OR_FAIL(c, grow(c->ev_bulk, hipEventDisableTiming));
+    HIP_OR_FAIL(c, grow(c->ev_up, hipEventDisableTiming));
     if ((int64_t)chunks > c->h_ctl_chunks) {
         if (c->h_ctl) (void)hipHostFree(c->h_ctl);
         c->h_ctl = nullptr;
@@ -2355,7 +2357,17 @@ int run_chunk(nw_ctx* c, OpsCall& o, int64_t k) {
     // same kernels runs 0.81 -> 0.69 ms; the pooled call's 96 small chunks lost: 16.61 vs 17.15 ms)
     p.lane = (!o.groups || o.dual) && hi - lo >= 65536;
     p.wide_first_ok = nchunks == 1 && !o.groups && !o.dual;   // (a one-chunk call: the other compute stream is idle)
-    if (pk && o.upload && !c->ac.use_diag) {   // the exact kernels read bytes: the chunk's bases -> bytes + exceptions
+    // A dual call unpacks each read range once, in its pass-0 chunk, when either pass runs the exact
+    // kernels on bytes: the unpack stores a decoded 'A' at every exception's place before its second
+    // launch corrects it, and no kernel of the other pass may see that (across the passes
+    // only a byte's final value is ever stored).  The pass-1 twin waits for the unpacked bytes (and the
+    // offsets rebuilt with them) instead of writing them again; a band-path pass beside it stores final
+    // values only (classify's write_read_bytes).
+    const bool dual_unpack = pk && o.upload && o.dual && !(o.gcfg[0].use_diag && o.gcfg[1].use_diag);
+    if (dual_unpack && pass == 1) {
+        HIP_OR_FAIL(c, hipStreamWaitEvent(p.cs, c->ev_up[(size_t)ch.up], 0));
+    } else if (pk && o.upload && (!c->ac.use_diag || dual_unpack)) {
+        // the exact kernels read bytes: the chunk's bases -> bytes + exceptions
         const int64_t b0 = offsets[lo], b1 = offsets[hi];
         const int64_t e0 = std::lower_bound(pk->exc_pos, pk->exc_pos + pk->n_exc, b0) - pk->exc_pos;
         const int64_t e1 = std::lower_bound(pk->exc_pos, pk->exc_pos + pk->n_exc, b1) - pk->exc_pos;
@@ -2366,7 +2378,9 @@ int run_chunk(nw_ctx* c, OpsCall& o, int64_t k) {
         const nw::LenSeg* ls = o.lens_on ? &lsk : nullptr;
         HIP_OR_FAIL(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, o.P0, b0, b1, c->d_exc_pos.p, c->d_exc_byte.p,
                                          e0, e1, c->d_reads.p, c->reads_bias, p.cs, ls));
-    } else if ((pk && o.upload) || o.packed_resident) {
+        if (dual_unpack) HIP_OR_FAIL(c, hipEventRecord(c->ev_up[(size_t)k], p.cs));
+    }
+    if (c->ac.use_diag && ((pk && o.upload) || o.packed_resident)) {
         // band path: classify decodes the chunk from the 2-bit stream itself (rebuilding its
         // offsets from the lengths) and writes only the bytes of the reads that need the DP --
         // no unpack launch, and 2 bits per base read instead of a byte written and re-read

@@ -89,7 +89,7 @@ __global__ __launch_bounds__(256) void nw_unpack_kernel(const uint32_t* packed, 
 __global__ __launch_bounds__(256) void nw_exceptions_kernel(const int64_t* pos, const uint8_t* byte, int64_t e0,
                                                             int64_t e1, uint8_t* dst, int64_t bias) {
     const int64_t e = e0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e < e1) dst[pos[e] - bias] = byte[e];
+    if (e < e1) dst[pos[e] - bias] = pk_exc_store_byte(byte[e]);
 }
 
 }  // namespace
