@@ -365,6 +365,11 @@ __device__ __forceinline__ bool cert_sub3(const KernelArgs& a, const unsigned* a
 // The one-indel certificate (classify, below; lanes ci: reads of La -+ kab bases, 1 <= kab <= the
 // certificate's largest gap, at batch position my_off).  True: certified, *gk_ the gap's read index q
 // (runs M q, the gap, M the rest).  Called by the whole wavefront.
+// ONEPASS: the candidate's own two diagonals (shifts 0 and kab, the only scans that run to the gap -- between
+// them nearly every word of the read) in one unrolled pass without exit tests; false: by the `ends` scans,
+// as every other shift (CRISPR_NW_INDEL_ONEPASS=0: the reference the tests hold the pass to).  A template
+// parameter: the kernel's code has to fit the instruction cache.
+template <bool ONEPASS>
 __device__ __forceinline__ bool cert_indel(const KernelArgs& a, const unsigned* amp2s, bool ci, long long my_off, int my_len,
                                            int* gk_) {
     const int La = a.La, n2 = (La + 15) / 16 + 2, sc5 = a.band_maxsub / 5;
@@ -396,8 +401,24 @@ __device__ __forceinline__ bool cert_indel(const KernelArgs& a, const unsigned* 
     // registers, picked per lane (deletion and insertion reads in one pass over the shifts)
     if (ci) {
         auto am = [&](int t) -> unsigned { return t < n2 ? amp2s[t] : 0u; };
-        auto wl = [&](int t) -> unsigned { return del ? am(t) : rw[t]; };
-        auto ws = [&](int t) -> unsigned { return del ? rw[t] : am(t); };
+        // (ONEPASS: picked once, by selects -- the amplicon's words past its last read as its spare zero word)
+        unsigned pl[18], ps[17];
+        if constexpr (ONEPASS) {
+#pragma unroll
+            for (int t = 0; t < 18; ++t) {
+                const unsigned av = amp2s[min(t, n2 - 1)];
+                pl[t] = del ? av : rw[t];
+                if (t < 17) ps[t] = del ? rw[t] : av;
+            }
+        }
+        auto wl = [&](int t) -> unsigned {
+            if constexpr (ONEPASS) return pl[t];
+            else return del ? am(t) : rw[t];
+        };
+        auto ws = [&](int t) -> unsigned {
+            if constexpr (ONEPASS) return ps[t];
+            else return del ? rw[t] : am(t);
+        };
         bool o = true;
         // first and last mismatch of a shift (one side's sequence shifted by sh against the
         // other's, P positions): scans from either end that stop as soon as every lane has found
@@ -443,16 +464,59 @@ __device__ __forceinline__ bool cert_indel(const KernelArgs& a, const unsigned* 
             return need <= 2 && c >= need;
         };
         int f0 = Ls, fmax_all = -1, fmax_1 = -1;
-        for (int sh = 0; sh <= kab; ++sh) {
-            int f, g;
-            ends(wl, ws, sh, Ls, &f, &g);
-            const int c = cnt(f, g, Ls);
-            o = o && mm * (Ls - c) - xx * c < S;
-            if (sh == 0) f0 = f;
-            if (sh > 0) o = o && g > (sh == kab ? fmax_1 : fmax_all);
-            if (sh == kab) gk = g;
-            fmax_all = max(fmax_all, f);
-            if (sh > 0) fmax_1 = max(fmax_1, f);
+        if constexpr (ONEPASS) {
+            // Shifts 0 and kab over all 17 words, no ballot and no exit: per word both mismatch masks (one bit
+            // per base, here the odd one: ((z << 1) | z) & mask is one instruction) under one length mask --
+            // 0xaaaaaaaa below the lane's last word wl_ = Ls >> 4, the partial mask pm there, 0 past it; wl_ and
+            // pm hoisted.  Shift 0 wants F (the first mismatch) and shift kab G (the last, + 1): the first / the
+            // last word with a nonzero mask and its index (a compare and two selects per word each), ctz / clz
+            // once after the loop.  The count classes (0, 1, >= 2 mismatches: what cnt takes from f and g) come
+            // from the masks' popcounts.  (126 VGPRs, as the scans' 127: 4 wavefronts per SIMD.)
+            const int wl_ = Ls >> 4;
+            const unsigned pm = (Ls & 15) ? 0xaaaaaaaau >> (32 - 2 * (Ls & 15)) : 0u;
+            const unsigned s2k = (unsigned)(2 * kab);
+            unsigned w0 = 0u, wk = 0u;   // shift 0's first nonzero mask word, shift kab's last
+            int i0 = 0, ik = 0, n0 = 0, nk = 0;   // their word indices; the two diagonals' mismatches
+#pragma unroll
+            for (int t = 0; t < 17; ++t) {
+                const unsigned vm = t < wl_ ? 0xaaaaaaaau : (t == wl_ ? pm : 0u);
+                const unsigned lo = wl(t), sw = ws(t);
+                const unsigned zk = __builtin_amdgcn_alignbit(wl(t + 1), lo, s2k) ^ sw, z0 = lo ^ sw;
+                const unsigned mk = ((zk << 1) | zk) & vm, m0 = ((z0 << 1) | z0) & vm;
+                nk += __builtin_popcount(mk);
+                n0 += __builtin_popcount(m0);
+                wk = mk != 0u ? mk : wk;   // the last nonzero word so far
+                ik = mk != 0u ? t : ik;
+                i0 = w0 == 0u ? t : i0;    // the first: words are taken while none was nonzero
+                w0 = w0 == 0u ? m0 : w0;
+            }
+            f0 = w0 != 0u ? 16 * i0 + (int)(__builtin_ctz(w0) >> 1) : Ls;
+            gk = wk != 0u ? 16 * ik + (int)((31 - __builtin_clz(wk)) >> 1) + 1 : 0;
+            const int c0 = min(n0, 2), ck = min(nk, 2);
+            const bool o0 = mm * (Ls - c0) - xx * c0 < S, ok_k = mm * (Ls - ck) - xx * ck < S;
+            o = o0;   // shift 0; its F seeds the running maximum
+            fmax_all = f0;
+            for (int sh = 1; sh < kab; ++sh) {
+                int f, g;
+                ends(wl, ws, sh, Ls, &f, &g);
+                const int c = cnt(f, g, Ls);
+                o = o && mm * (Ls - c) - xx * c < S && g > fmax_all;
+                fmax_all = max(fmax_all, f);
+                fmax_1 = max(fmax_1, f);
+            }
+            o = o && ok_k && gk > fmax_1;   // shift kab, against shifts 1 .. kab - 1
+        } else {
+            for (int sh = 0; sh <= kab; ++sh) {
+                int f, g;
+                ends(wl, ws, sh, Ls, &f, &g);
+                const int c = cnt(f, g, Ls);
+                o = o && mm * (Ls - c) - xx * c < S;
+                if (sh == 0) f0 = f;
+                if (sh > 0) o = o && g > (sh == kab ? fmax_1 : fmax_all);
+                if (sh == kab) gk = g;
+                fmax_all = max(fmax_all, f);
+                if (sh > 0) fmax_1 = max(fmax_1, f);
+            }
         }
         for (int sh = kab + 1; sh <= kab + 3; ++sh) o = o && enough(wl, ws, sh, Ll - sh);
         for (int sh = 1; sh <= 3; ++sh) o = o && enough(ws, wl, sh, Ls - sh);   // s shifted against l
@@ -549,7 +613,7 @@ __device__ __forceinline__ void write_read_bytes(const KernelArgs& a, unsigned l
 
 
 // (5 wavefronts per SIMD; forced to 6 / 8 with 31 / 60 VGPRs spilled it ran 0.188 / 0.223 vs 0.150 ms per resident
-// pass in round 5)
+// pass in round 5; at 6 again once nothing spilled at 5: 39 spilled, 0.350 vs 0.327 ms)
 #ifndef NW_CLASSIFY_WPE
 #define NW_CLASSIFY_WPE 5
 #endif
@@ -1306,6 +1370,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NW_CLASSIFY
 // ============================================================================
 constexpr int kCertSlots = 16;   // classify wavefronts per block (4 classify blocks)
 
+// ONEPASS: cert_indel's form (KernelArgs::indel_onepass)
+template <bool ONEPASS>
 __global__ __launch_bounds__(256) void nw_band_cert(const KernelArgs a, int nslots) {
     extern __shared__ unsigned c_amp2[];   // the amplicon's 2-bit words (classify's image from 2 nd)
     __shared__ int s_n3[kCertSlots], s_ni[kCertSlots], s_o3[kCertSlots + 1], s_oi[kCertSlots + 1];
@@ -1371,7 +1437,7 @@ __global__ __launch_bounds__(256) void nw_band_cert(const KernelArgs a, int nslo
         const long long my_off = v ? a.offsets[r] : a.pk_pos0;
         const int my_len = v ? (int)(a.offsets[r + 1] - my_off) : La;
         int gk = 0;
-        const bool ok = cert_indel(a, c_amp2, v, my_off, my_len, &gk);
+        const bool ok = cert_indel<ONEPASS>(a, c_amp2, v, my_off, my_len, &gk);
         if (ok) {   // runs M q, the gap (X: residues of the read, Y: of the amplicon), M the rest of the shorter
             const bool del = my_len < La;
             const int Ls = del ? my_len : La, kab = del ? La - my_len : my_len - La;
@@ -1402,8 +1468,10 @@ void launch_band_classify(const KernelArgs& a, hipStream_t s) {
             hipLaunchKernelGGL((nw_band_classify<true, false>), dim3((unsigned)(g1 - g0 + 1)), dim3(256), lds, s, a);
         if (a.cert_q) {   // its four wavefronts' queues per block
             const int nslots = (int)(4 * (g1 - g0 + 1));
-            hipLaunchKernelGGL(nw_band_cert, dim3((unsigned)((nslots + kCertSlots - 1) / kCertSlots)), dim3(256),
-                               (size_t)(4 * ((a.La + 15) / 16 + 2)), s, a, nslots);
+            const dim3 grid((unsigned)((nslots + kCertSlots - 1) / kCertSlots));
+            const size_t clds = (size_t)(4 * ((a.La + 15) / 16 + 2));
+            if (a.indel_onepass) hipLaunchKernelGGL(nw_band_cert<true>, grid, dim3(256), clds, s, a, nslots);
+            else hipLaunchKernelGGL(nw_band_cert<false>, grid, dim3(256), clds, s, a, nslots);
         }
     } else {
         hipLaunchKernelGGL(nw_band_classify<false>, dim3(std::max(1, std::min(2048, (int)((a.n + 255) / 256)))),

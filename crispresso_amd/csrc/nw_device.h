@@ -148,6 +148,7 @@ struct KernelArgs {
     // diagonals from them (0: from word passes over the read)
     int32_t sub12_words, sub12_table;
     int32_t amp_acgt;              // every amplicon byte A C G T (either case)
+    int32_t indel_onepass;         // nw_band_cert: the one-indel candidate's two diagonals in one pass (0: by scans)
     // known copies: the 2-bit words of a sequence of the amplicon's length whose
     // alignment against the amplicon is computed once (the previous amplicon of a resident batch:
     // the HDR pass's reads that are copies of the reference amplicon); classify flags the reads equal

@@ -117,6 +117,7 @@ struct Switches {
     bool wide_first = true;            // CRISPR_NW_WIDE_FIRST "0": no wide-first list (its reads wait for the wide level)
     int64_t wide_first_cap = 2 * kWideFirstPairs;   // CRISPR_NW_WIDE_FIRST_CAP: reads of a chunk's list run beside the first level
     bool sub12_table = true;           // CRISPR_NW_SUB12_TABLE "0": classify's one- / two-substitution checks by word passes
+    bool indel_onepass = true;         // CRISPR_NW_INDEL_ONEPASS "0": the one-indel check's two long diagonals by scans
     int direct = -1;                   // CRISPR_NW_DIRECT: reads up to which the first level hands straight to the wide level
     bool l1skip = true;                // CRISPR_NW_L1SKIP "0": chunks of >= 65536 reads with few DP reads keep the first level
     bool adapt = true;                 // CRISPR_NW_ADAPT "0": no adaptive level choice across chunks
@@ -147,6 +148,7 @@ static Switches read_switches() {
     w.wide_first = !off("CRISPR_NW_WIDE_FIRST");
     if (const char* e = std::getenv("CRISPR_NW_WIDE_FIRST_CAP")) w.wide_first_cap = std::max(0ll, std::atoll(e));
     w.sub12_table = !off("CRISPR_NW_SUB12_TABLE");
+    w.indel_onepass = !off("CRISPR_NW_INDEL_ONEPASS");
     if (const char* e = std::getenv("CRISPR_NW_DIRECT")) w.direct = std::max(0, std::atoi(e));
     w.l1skip = !off("CRISPR_NW_L1SKIP");
     if (const char* e = std::getenv("CRISPR_NW_ADAPT")) w.adapt = std::strcmp(e, "0") != 0;
@@ -1197,6 +1199,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
         a.cls_words = c->cur.cls_words;
         a.sub12_words = c->cur.sub12_words;
         a.sub12_table = p.sw->sub12_table ? 1 : 0;
+        a.indel_onepass = p.sw->indel_onepass ? 1 : 0;
         a.amp_acgt = c->cur.amp_acgt ? 1 : 0;
         // seeded band: the packed classify marks the reads, the segment sort lists them apart
         // (sorted by their hits' diagonals), the wide level takes that list after its own
