@@ -74,7 +74,7 @@ COUNT_EXPORTS = (
 REGION_EXPORTS = (
     "nwr_read_bam", "nwr_bam_free", "nwr_bam_count", "nwr_bam_data", "nwr_bam_offsets", "nwr_bam_n_ref",
     "nwr_bam_ref_names", "nwr_bam_ref_lens", "nwr_bam_text", "nwr_create", "nwr_destroy", "nwr_last_error",
-    "nwr_extract", "nwr_fetch", "nwr_release",
+    "nwr_extract", "nwr_fetch", "nwr_release", "nwr_discover", "nwr_fetch_regions",
 )
 NWR_MAX_REGIONS = 1 << 20
 NWR_BY_REFERENCE, NWR_EQX_AS_MATCH = 1, 2
@@ -340,6 +340,8 @@ def load() -> ctypes.CDLL:
         "nwr_extract": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_int32, POINTER(NwrResult)]),
         "nwr_fetch": (c_int, [POINTER(NwrResult)] + [c_void_p] * 7),
         "nwr_release": (None, [POINTER(NwrResult)]),
+        "nwr_discover": (c_int, [ctx_p, c_void_p, c_int32, c_int64, POINTER(NwrResult)]),
+        "nwr_fetch_regions": (c_int, [POINTER(NwrResult), c_void_p, c_void_p, c_void_p]),
         "nw_synth_offsets": (c_int64, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,
                                         c_int32]),
         "nw_synth_reads": (c_int, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,

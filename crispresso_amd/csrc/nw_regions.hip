@@ -21,6 +21,24 @@
 //           output offsets, nibbles through the 16-letter table (the parity of st + k picks the
 //           half), qualities + 33, one aligned dword store to text and one to quals.
 // No atomic arrival order reaches the result: the only atomics are sums of counters.
+//
+// nwr_discover (CRISPRessoPooled's genome mode, CRISPRessoPooledCORE.py:1045-1082) finds the
+// regions first, over the same chunks:
+//   span     a lane per record: the clip-extended span (ref, bpstart, bpend) of the header's walk,
+//            packed into two 64-bit words, looked up in an open-addressing table in HBM that lives
+//            for the call.  The probe starts at the slot of the key's hash; a slot is claimed by
+//            a 64-bit atomicCAS on its first word and then on its second, each word is written
+//            once and never changes, so a lane decides on what the CAS returned alone: the slot is
+//            its key's, or some other key's and it probes on.  No lane waits for another, keys
+//            with equal hashes part exactly, the probes are bounded by the table size.  The
+//            slot's count goes up by atomicAdd, the record keeps its slot (4 bytes a record).
+//   compact  a lane per slot: the used slots (slot, key, count) to a list for the host, which
+//            sorts the keys, applies min_reads and sends back region-or-none per listed slot.
+//   scatter  that answer to map[slot].
+//   mark / scan / write   per chunk as above: a record counts one hit iff map[slot] is a region;
+//            the hit (region, record) lands at its scanned index.  order and emit follow as above.
+// Which slot a key got depends on arrival order; the slot never leaves this file: the host orders
+// by key, and the hit list is in record order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -59,6 +77,8 @@ struct Args {
     int64_t blocks;
     unsigned long long* totals;
     uint4* hits;               // (region in table order, record of the chunk, st, en)
+    const uint32_t* slot;      // nwr_discover: [cn] the chunk's records' table slots, kNoSlot = not kept
+    const int32_t* map;        // nwr_discover: [cap] the slot's region, -1 = not emitted
 };
 
 struct EmitHit {
@@ -219,6 +239,217 @@ __global__ __launch_bounds__(kBlk) void nwr_write_kernel(const Args a) {
     });
 }
 
+// ---- nwr_discover ---------------------------------------------------------------------------
+
+constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
+constexpr uint64_t kHashMul = 0x9E3779B97F4A7C15ull;
+enum { kKept = 0, kDropped = 1, kAligned = 2, kDistinct = 3, kError = 4, kListed = 5, kCounters = 6 };
+
+// The table: word 0 of a slot is never 0 for a key (bpstart carries a bias), word 1 is stored
+// plus one; 0 is "empty" in both.
+struct Table {
+    unsigned long long* w0;
+    unsigned long long* w1;
+    uint32_t* count;
+    uint64_t cap_mask;
+    int shift;                 // 64 - log2(slots)
+    uint64_t hash_mask;        // CRISPR_NWR_HASH_BITS
+};
+
+struct SpanArgs {
+    const uint8_t* data;
+    const int64_t* off;
+    int32_t cn;
+    int32_t flags;
+    Table t;
+    uint32_t* slot;            // [cn]
+    unsigned long long* ctr;   // [kCounters]
+};
+
+struct Listed {
+    uint64_t w0, w1;
+    uint32_t slot, count;
+};
+
+// (ref, bpstart, bpend) in 16 bytes, exactly: ref < 2^31, |bpstart| < 2^46 and bpend - bpstart
+// < 2^45 (pos < 2^31, at most 65535 ops of under 2^28 each).
+constexpr int64_t kStartBias = (int64_t)1 << 47;
+__host__ __device__ inline void pack_key(int32_t ref, int64_t bs, int64_t be, uint64_t* w0, uint64_t* w1) {
+    *w0 = (uint64_t)(bs + kStartBias) | ((uint64_t)((uint32_t)ref & 0xFFFFu) << 48);
+    *w1 = (uint64_t)(be - bs) | ((uint64_t)((uint32_t)ref >> 16) << 48);
+}
+inline void unpack_key(uint64_t w0, uint64_t w1, nwr_region* r) {
+    const uint64_t m48 = ((uint64_t)1 << 48) - 1;
+    r->ref_id = (int32_t)((w0 >> 48) | ((w1 >> 48) << 16));
+    r->bpstart = (int64_t)(w0 & m48) - kStartBias;
+    r->bpend = r->bpstart + (int64_t)(w1 & m48);
+    r->reserved = 0;
+}
+
+__device__ inline uint64_t key_hash(uint64_t w0, uint64_t w1) {
+    uint64_t x = (w0 ^ (w1 * kHashMul)) * 0xD6E8FEB86659FD93ull;
+    x ^= x >> 32;
+    x *= 0xD6E8FEB86659FD93ull;
+    return x ^ (x >> 29);
+}
+
+// The span of the header's walk.  Kinds are BAM's op codes: M 0, I 1, D 2, N 3, S 4, H 5, P 6.
+__device__ inline void span_step(uint32_t kind, int64_t len, int64_t pos, int64_t* bs, int64_t* be) {
+    if (kind == 4) {
+        if (*be == pos) *bs -= len;
+        else *be += len;
+    } else if (kind != 1 && kind != 5) {
+        *be += len;
+    }
+}
+
+__global__ __launch_bounds__(kBlk) void nwr_span_kernel(const SpanArgs a) {
+    __shared__ uint32_t part[kBlk / 64][4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    uint32_t kept = 0, dropped = 0, aligned = 0, fresh = 0;
+    if (i < a.cn) {
+        const uint8_t* r = a.data + a.off[i];
+        const int32_t ref = (int32_t)ld32(r + nw_bam::kRefId);
+        const uint32_t flag = ld16(r + nw_bam::kFlag);
+        aligned = (flag & 0x904u) == 0;
+        uint32_t found = kNoSlot;
+        if (!(flag & 4u) && ref >= 0) {
+            const int32_t n_op = (int32_t)ld16(r + nw_bam::kNCigar), l_seq = (int32_t)ld32(r + nw_bam::kLSeq);
+            const uint8_t* cig = r + nw_bam::kName + r[nw_bam::kLReadName];
+            if (!(l_seq > 0 && cig[4 * (int64_t)n_op + (l_seq + 1) / 2] != 0xFF)) {
+                dropped = 1;
+            } else {
+                const bool eqx = (a.flags & NWR_EQX_AS_MATCH) != 0;
+                const int64_t pos = (int64_t)(int32_t)ld32(r + nw_bam::kPos) + 1;
+                int64_t bs = pos, be = pos, run = -1;      // run: the length a run of unsplit ops carries
+                for (int k = 0; k < n_op; ++k) {
+                    const uint32_t v = ld32(cig + 4 * k);
+                    uint32_t op = v & 15u;
+                    int64_t len = v >> 4;
+                    if (op >= 7) {
+                        if (eqx) {
+                            if (op > 8) continue;
+                            op = 0;
+                        } else {
+                            if (run < 0) run = len;
+                            continue;
+                        }
+                    }
+                    if (run >= 0) len = run, run = -1;
+                    span_step(op, len, pos, &bs, &be);
+                }
+                if (run >= 0) span_step(0, run, pos, &bs, &be);
+                uint64_t w0, w1;
+                pack_key(ref, bs, be, &w0, &w1);
+                w1 += 1;
+                uint64_t s = ((key_hash(w0, w1) & a.t.hash_mask) * kHashMul) >> a.t.shift;
+                for (uint64_t probe = 0; probe <= a.t.cap_mask; ++probe) {      // bounded by the table size
+                    unsigned long long x = __hip_atomic_load(&a.t.w0[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (x == 0) {
+                        x = atomicCAS(&a.t.w0[s], 0ull, (unsigned long long)w0);
+                        if (x == 0) x = w0;
+                    }
+                    if (x == w0) {
+                        unsigned long long y = __hip_atomic_load(&a.t.w1[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (y == 0) {
+                            y = atomicCAS(&a.t.w1[s], 0ull, (unsigned long long)w1);
+                            if (y == 0) y = w1, fresh = 1;
+                        }
+                        if (y == w1) {
+                            atomicAdd(&a.t.count[s], 1u);
+                            found = (uint32_t)s;
+                            break;
+                        }
+                    }
+                    s = (s + 1) & a.t.cap_mask;
+                }
+                if (found == kNoSlot) a.ctr[kError] = 1;      // a full table: cannot happen at load <= 1/2
+                else kept = 1;
+            }
+        }
+        a.slot[i] = found;
+    }
+    uint32_t v0 = kept, v1 = dropped, v2 = aligned, v3 = fresh;
+    for (int s = 32; s > 0; s >>= 1) {
+        v0 += __shfl_xor(v0, s);
+        v1 += __shfl_xor(v1, s);
+        v2 += __shfl_xor(v2, s);
+        v3 += __shfl_xor(v3, s);
+    }
+    if (lane == 0) part[wave][0] = v0, part[wave][1] = v1, part[wave][2] = v2, part[wave][3] = v3;
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        uint32_t sum = 0;
+        for (int w = 0; w < kBlk / 64; ++w) sum += part[w][threadIdx.x];
+        if (sum) atomicAdd(&a.ctr[threadIdx.x], (unsigned long long)sum);      // (sums: no order shows)
+    }
+}
+
+// The used slots to list[0 .. ctr[kListed]) in any order (the host sorts by key); cap entries
+// at most are written.
+__global__ __launch_bounds__(kBlk) void nwr_compact_kernel(const Table t, Listed* list, uint64_t cap,
+                                                           unsigned long long* ctr) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t s = (uint64_t)blockIdx.x * kBlk + threadIdx.x;
+    const bool used = s <= t.cap_mask && t.w1[s] != 0;
+    const unsigned long long b = __ballot(used);
+    if (!b) return;
+    const int lead = __ffsll((long long)b) - 1;
+    unsigned long long at = 0;
+    if (lane == lead) at = atomicAdd(&ctr[kListed], (unsigned long long)__popcll(b));
+    at = __shfl(at, lead, 64) + (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
+    if (used && at < cap) list[at] = Listed{t.w0[s], t.w1[s] - 1, (uint32_t)s, t.count[s]};
+}
+
+__global__ __launch_bounds__(kBlk) void nwr_scatter_kernel(const uint32_t* slots, const int32_t* reg, int64_t n,
+                                                           uint64_t cap_mask, int32_t* map) {
+    const int64_t e = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (e < n && slots[e] <= cap_mask) map[slots[e]] = reg[e];
+}
+
+__device__ inline uint32_t mark_of(const Args& a, int64_t i) {
+    if (i >= a.cn) return 0;
+    const uint32_t s = a.slot[i];
+    return s != kNoSlot && a.map[s] >= 0;
+}
+
+__global__ __launch_bounds__(kBlk) void nwr_mark_kernel(const Args a) {
+    __shared__ uint32_t part[kBlk / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    const uint32_t cnt = mark_of(a, i);
+    if (i < a.cn) a.counts[i] = cnt;
+    uint32_t v0 = cnt;
+    for (int s = 32; s > 0; s >>= 1) v0 += __shfl_xor(v0, s);
+    if (lane == 0) part[wave] = v0;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s0 = 0;
+        for (int w = 0; w < kBlk / 64; ++w) s0 += part[w];
+        a.sums[blockIdx.x] = s0;
+        if (s0) atomicAdd(&a.totals[kHits], (unsigned long long)s0);
+    }
+}
+
+// (region, record, 0, 0): the host fills en = l_seq, so this step reads no record byte.
+__global__ __launch_bounds__(kBlk) void nwr_mark_write_kernel(const Args a) {
+    __shared__ uint32_t part[kBlk / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t i = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    const uint32_t cnt = i < a.cn ? a.counts[i] : 0u;
+    uint32_t x = cnt;
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t y = __shfl_up(x, s);
+        if (lane >= s) x += y;
+    }
+    if (lane == 63) part[wave] = x;
+    __syncthreads();
+    uint32_t at = a.sums[blockIdx.x] + x - cnt;
+    for (int w = 0; w < wave; ++w) at += part[w];
+    if (cnt) a.hits[at] = make_uint4((uint32_t)a.map[a.slot[i]], (uint32_t)i, 0u, 0u);
+}
+
 // "=ACMGRSVTWYHKDBN" as two little-endian words
 constexpr uint64_t kNibLo = 0x565352474D43413Dull, kNibHi = 0x4E42444B48595754ull;
 
@@ -289,6 +520,11 @@ struct Hits {
 struct Result {
     std::vector<int64_t> region_off;
     Hits h;
+    // nwr_discover: the regions in result order, their whole-call counts, nwr_fetch_regions' stats
+    bool discovered = false;
+    std::vector<nwr_region> regions;
+    std::vector<int64_t> n_records;
+    int64_t stats[4] = {0, 0, 0, 0};
 };
 
 }  // namespace nwr
@@ -306,6 +542,12 @@ struct nwr_ctx {
     nwr::Buf<unsigned long long> d_totals;
     nwr::Buf<uint4> d_hits;
     nwr::Buf<nwr::EmitHit> d_eh;
+    // nwr_discover
+    int hash_bits = 64;             // CRISPR_NWR_HASH_BITS
+    nwr::Buf<unsigned long long> d_w0, d_w1, d_ctr;
+    nwr::Buf<uint32_t> d_tcount, d_slot, d_lslot;
+    nwr::Buf<int32_t> d_map, d_lreg;
+    nwr::Buf<nwr::Listed> d_list;
 };
 
 namespace {
@@ -330,6 +572,103 @@ int rfail(nwr_ctx* c, int code, const char* fmt, ...) {
 
 inline uint32_t h16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 inline uint32_t h32(const uint8_t* p) { return h16(p) | (h16(p + 2) << 16); }
+
+int finish_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, const std::vector<int64_t>& off, nwr::Args a,
+                 int64_t nh, void (*write_kernel)(const nwr::Args), bool whole, const std::vector<int32_t>& perm,
+                 int64_t n_regions, std::vector<int64_t>* cursor, nwr::Hits* out, float* kernel_ms);
+
+// Where the chunk that starts at record r0 ends.
+int64_t chunk_end(const nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t n) {
+    if (c->chunk_records > 0) return std::min(n, r0 + c->chunk_records);
+    const int64_t r1 = std::min(n, r0 + nwr::kChunkRecords);
+    const int64_t* o = bam->off.data();
+    const int64_t* e = std::upper_bound(o + r0 + 1, o + r1 + 1, o[r0] + nwr::kChunkBytes);
+    return std::max<int64_t>(r0 + 1, (e - o) - 1);      // (one record at least, whatever its size)
+}
+
+// The chunk's records and their starts to d_data / d_off; off gets the starts.
+int upload_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, bool offsets_too, std::vector<int64_t>* off,
+                 float* upload_ms) {
+    const int64_t cn = r1 - r0, base = bam->off[(size_t)r0], nbytes = bam->off[(size_t)r1] - base;
+    off->resize((size_t)cn + 1);
+    for (int64_t i = 0; i <= cn; ++i) (*off)[(size_t)i] = bam->off[(size_t)(r0 + i)] - base;
+    if (!upload_ms) return NW_OK;      // (the records are in d_data already)
+    RHIP(c, c->d_data.reserve((size_t)nbytes));
+    RHIP(c, c->d_off.reserve((size_t)cn + 1));
+    const auto t0 = std::chrono::steady_clock::now();
+    RHIP(c, hipMemcpyAsync(c->d_data.p, bam->data.data() + base, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
+    if (offsets_too)
+        RHIP(c, hipMemcpyAsync(c->d_off.p, off->data(), sizeof(int64_t) * (size_t)(cn + 1), hipMemcpyHostToDevice, c->stream));
+    RHIP(c, hipStreamSynchronize(c->stream));
+    *upload_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return NW_OK;
+}
+
+// Pass 1 of nwr_discover over one chunk: spans into the table, the records' slots.
+int span_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, int32_t flags, const nwr::Table& t, float* kernel_ms,
+               float* upload_ms) {
+    std::vector<int64_t> off;
+    const int rc = upload_chunk(c, bam, r0, r1, true, &off, upload_ms);
+    if (rc != NW_OK) return rc;
+    nwr::SpanArgs sa{};
+    sa.data = c->d_data.p;
+    sa.off = c->d_off.p;
+    sa.cn = (int32_t)(r1 - r0);
+    sa.flags = flags;
+    sa.t = t;
+    sa.slot = c->d_slot.p + r0;
+    sa.ctr = c->d_ctr.p;
+    RHIP(c, hipEventRecord(c->ev[0], c->stream));
+    hipLaunchKernelGGL(nwr::nwr_span_kernel, dim3((unsigned)((sa.cn + nwr::kBlk - 1) / nwr::kBlk)), dim3(nwr::kBlk), 0, c->stream, sa);
+    RHIP(c, hipGetLastError());
+    RHIP(c, hipEventRecord(c->ev[1], c->stream));
+    RHIP(c, hipStreamSynchronize(c->stream));
+    float ms = 0.0f;
+    RHIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    *kernel_ms += ms;
+    return NW_OK;
+}
+
+// Pass 2 over one chunk: the records of the emitted regions as hits, ordered and emitted.
+int emit_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, int32_t flags, bool resident, int64_t n_regions,
+               std::vector<int64_t>* cursor, nwr::Hits* out, float* kernel_ms, float* upload_ms) {
+    hipStream_t st = c->stream;
+    const int64_t cn = r1 - r0, blocks = (cn + nwr::kBlk - 1) / nwr::kBlk;
+    RHIP(c, c->d_counts.reserve((size_t)cn));
+    RHIP(c, c->d_sums.reserve((size_t)blocks));
+    RHIP(c, c->d_totals.reserve(2));
+    RHIP(c, hipMemsetAsync(c->d_totals.p, 0, 2 * sizeof(unsigned long long), st));
+    nwr::Args a{};
+    a.cn = (int32_t)cn;
+    a.flags = flags;
+    a.counts = c->d_counts.p;
+    a.sums = c->d_sums.p;
+    a.blocks = blocks;
+    a.totals = c->d_totals.p;
+    a.slot = c->d_slot.p + r0;
+    a.map = c->d_map.p;
+    RHIP(c, hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(nwr::nwr_mark_kernel, dim3((unsigned)blocks), dim3(nwr::kBlk), 0, st, a);
+    RHIP(c, hipGetLastError());
+    RHIP(c, hipEventRecord(c->ev[1], st));
+    unsigned long long totals[2] = {0, 0};
+    RHIP(c, hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, st));
+    RHIP(c, hipStreamSynchronize(st));
+    float ms = 0.0f;
+    RHIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    *kernel_ms += ms;
+    const int64_t nh = (int64_t)totals[nwr::kHits];
+    if (nh > nwr::kMaxHits)
+        return rfail(c, NW_E_UNSUPPORTED, "%lld hits in the chunk of records %lld to %lld: at most 2^30 (use a smaller CRISPR_NWR_CHUNK)",
+                     (long long)nh, (long long)r0, (long long)r1);
+    if (nh == 0) return NW_OK;      // (a chunk of off-target records alone is not uploaded again)
+    std::vector<int64_t> off;
+    const int rc = upload_chunk(c, bam, r0, r1, false, &off, resident ? nullptr : upload_ms);
+    if (rc != NW_OK) return rc;
+    a.data = c->d_data.p;
+    static const std::vector<int32_t> no_perm;
+    return finish_chunk(c, bam, r0, r1, off, a, nh, nwr::nwr_mark_write_kernel, true, no_perm, n_regions, cursor, out, kernel_ms);
+}
 
 // One chunk: records [r0, r1) of bam; its hits in region-major order (the caller's regions).
 int run_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, nwr::Args a, const std::vector<int32_t>& perm,
@@ -373,13 +712,24 @@ int run_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, nwr::Args 
         return rfail(c, NW_E_UNSUPPORTED, "%lld hits in the chunk of records %lld to %lld: at most 2^30 (use a smaller CRISPR_NWR_CHUNK)",
                      (long long)nh, (long long)r0, (long long)r1);
     if (nh == 0) return NW_OK;
+    return finish_chunk(c, bam, r0, r1, off, a, nh, nwr::nwr_write_kernel, false, perm, n_regions, cursor, out, kernel_ms);
+}
 
+// The rest of a chunk once its hits are counted (a.counts, a.sums, nh of them) and its records
+// are in d_data: scan, write, the host's order step, emit.  `whole`: the hits carry no st / en,
+// every read is its record's whole sequence (nwr_discover).
+int finish_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, const std::vector<int64_t>& off, nwr::Args a,
+                 int64_t nh, void (*write_kernel)(const nwr::Args), bool whole, const std::vector<int32_t>& perm,
+                 int64_t n_regions, std::vector<int64_t>* cursor, nwr::Hits* out, float* kernel_ms) {
+    hipStream_t st = c->stream;
+    const int64_t cn = r1 - r0, blocks = a.blocks;
+    float ms = 0.0f;
     RHIP(c, c->d_hits.reserve((size_t)nh));
     a.hits = c->d_hits.p;
     RHIP(c, hipEventRecord(c->ev[2], st));
     hipLaunchKernelGGL(nwr::nwr_scan_kernel, dim3(1), dim3(nwr::kScanBlk), 0, st, a);
     RHIP(c, hipGetLastError());
-    hipLaunchKernelGGL(nwr::nwr_write_kernel, dim3((unsigned)blocks), dim3(nwr::kBlk), 0, st, a);
+    hipLaunchKernelGGL(write_kernel, dim3((unsigned)blocks), dim3(nwr::kBlk), 0, st, a);
     RHIP(c, hipGetLastError());
     RHIP(c, hipEventRecord(c->ev[3], st));
     std::vector<uint4> hits((size_t)nh);
@@ -389,7 +739,7 @@ int run_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, nwr::Args 
     *kernel_ms += ms;
 
     // region-major, record order within a region: a stable counting sort on the caller's region
-    const bool by_ref = (a.flags & NWR_BY_REFERENCE) != 0;
+    const bool by_ref = whole || (a.flags & NWR_BY_REFERENCE) != 0;      // the hit's region is the caller's already
     std::vector<int64_t>& cur = *cursor;
     std::fill(cur.begin(), cur.end(), 0);
     for (const uint4& h : hits) {
@@ -404,11 +754,12 @@ int run_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, nwr::Args 
     out->en.resize((size_t)nh);
     std::vector<nwr::EmitHit> eh((size_t)nh);
     std::vector<int32_t> len((size_t)nh);
-    for (const uint4& h : hits) {
+    for (uint4 h : hits) {
         const int32_t g = by_ref ? (int32_t)h.x : perm[h.x];
         const size_t k = (size_t)cur[(size_t)g]++;
         const uint8_t* r = bam->data.data() + bam->off[(size_t)(r0 + h.y)];
         const int64_t l_seq = (int32_t)h32(r + nw_bam::kLSeq);
+        if (whole) h.z = 0, h.w = (uint32_t)l_seq;
         const int64_t s = std::min<int64_t>((int32_t)h.z, l_seq), e = std::min<int64_t>((int32_t)h.w, l_seq);
         out->reg[k] = g;
         out->src[k] = r0 + h.y;
@@ -525,6 +876,7 @@ int nwr_create(int device, nwr_ctx** out) {
     }
     if (const char* e = std::getenv("CRISPR_NWR_CHUNK"))
         c->chunk_records = std::max<int64_t>(0, std::min<int64_t>(std::atoll(e), nwr::kChunkRecords));
+    if (const char* e = std::getenv("CRISPR_NWR_HASH_BITS")) c->hash_bits = std::max(0, std::min(64, std::atoi(e)));
     *out = c;
     return NW_OK;
 }
@@ -545,6 +897,15 @@ void nwr_destroy(nwr_ctx* c) {
     c->d_totals.release();
     c->d_hits.release();
     c->d_eh.release();
+    c->d_w0.release();
+    c->d_w1.release();
+    c->d_ctr.release();
+    c->d_tcount.release();
+    c->d_slot.release();
+    c->d_lslot.release();
+    c->d_map.release();
+    c->d_lreg.release();
+    c->d_list.release();
     for (hipEvent_t e : c->ev)
         if (e) (void)hipEventDestroy(e);
     if (c->stream) (void)hipStreamDestroy(c->stream);
@@ -615,15 +976,7 @@ int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64
     std::vector<nwr::Hits> chunks;
     std::vector<int64_t> cursor((size_t)n_regions + 1);
     for (int64_t r0 = 0; r0 < n;) {
-        int64_t r1;
-        if (c->chunk_records > 0) {
-            r1 = std::min(n, r0 + c->chunk_records);
-        } else {
-            r1 = std::min(n, r0 + nwr::kChunkRecords);
-            const int64_t* o = bam->off.data();
-            const int64_t* e = std::upper_bound(o + r0 + 1, o + r1 + 1, o[r0] + nwr::kChunkBytes);
-            r1 = std::max<int64_t>(r0 + 1, (e - o) - 1);      // (one record at least, whatever its size)
-        }
+        const int64_t r1 = chunk_end(c, bam, r0, n);
         nwr::Hits h;
         rc = run_chunk(c, bam, r0, r1, a, perm, n_regions, &cursor, &h, &res->n_no_seq, &res->kernel_ms, &res->upload_ms);
         if (rc != NW_OK) return bail(rc);
@@ -633,6 +986,167 @@ int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64
     merge_chunks(chunks, n_regions, R);
     res->n_hits = (int64_t)R->h.reg.size();
     res->n_bytes = R->h.toff.back();
+    return NW_OK;
+}
+
+int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_reads, nwr_result* res) {
+    if (!c) return NW_E_INVALID;
+    if (!bam || !res) return rfail(c, NW_E_INVALID, "null argument");
+    std::memset(res, 0, sizeof *res);
+    if (flags & ~NWR_EQX_AS_MATCH) return rfail(c, NW_E_INVALID, "unknown flags %d", (int)flags);
+    const int64_t n = (int64_t)bam->off.size() - 1;
+    if (n > ((int64_t)1 << 30))
+        return rfail(c, NW_E_UNSUPPORTED, "%lld records: at most 2^30 in one nwr_discover call", (long long)n);
+    nwr::Result* R = new nwr::Result();
+    R->discovered = true;
+    R->region_off.assign(1, 0);
+    res->handle = R;
+    if (n <= 0) return NW_OK;
+    if (hipSetDevice(c->device) != hipSuccess) {
+        delete R;
+        res->handle = nullptr;
+        return rfail(c, NW_E_HIP, "hipSetDevice failed");
+    }
+
+    std::vector<nwr::Hits> chunks;
+    int64_t n_regions = 0;
+    const int rc = [&]() -> int {
+        hipStream_t st = c->stream;
+        // the table: a power of two of at least twice the records, so the load stays <= 1/2
+        int log2 = 10;
+        while (((int64_t)1 << log2) < 2 * n) ++log2;
+        const size_t slots = (size_t)1 << log2;
+        RHIP(c, c->d_w0.reserve(slots));
+        RHIP(c, c->d_w1.reserve(slots));
+        RHIP(c, c->d_tcount.reserve(slots));
+        RHIP(c, c->d_slot.reserve((size_t)n));
+        RHIP(c, c->d_ctr.reserve(nwr::kCounters));
+        RHIP(c, hipMemsetAsync(c->d_w0.p, 0, sizeof(unsigned long long) * slots, st));
+        RHIP(c, hipMemsetAsync(c->d_w1.p, 0, sizeof(unsigned long long) * slots, st));
+        RHIP(c, hipMemsetAsync(c->d_tcount.p, 0, sizeof(uint32_t) * slots, st));
+        RHIP(c, hipMemsetAsync(c->d_ctr.p, 0, sizeof(unsigned long long) * nwr::kCounters, st));
+        nwr::Table t{};
+        t.w0 = c->d_w0.p;
+        t.w1 = c->d_w1.p;
+        t.count = c->d_tcount.p;
+        t.cap_mask = (uint64_t)slots - 1;
+        t.shift = 64 - log2;
+        t.hash_mask = c->hash_bits >= 64 ? ~0ull : (((uint64_t)1 << c->hash_bits) - 1);
+
+        std::vector<std::pair<int64_t, int64_t>> ranges;
+        for (int64_t r0 = 0; r0 < n; r0 = ranges.back().second) ranges.emplace_back(r0, chunk_end(c, bam, r0, n));
+        for (const auto& r : ranges) {
+            const int rc1 = span_chunk(c, bam, r.first, r.second, flags, t, &res->kernel_ms, &res->upload_ms);
+            if (rc1 != NW_OK) return rc1;
+        }
+        unsigned long long ctr[nwr::kCounters];
+        RHIP(c, hipMemcpy(ctr, c->d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
+        if (ctr[nwr::kError])
+            return rfail(c, NW_E_STATE, "the span table's probe bound was reached (%zu slots, %lld records)", slots, (long long)n);
+        const int64_t nd = (int64_t)ctr[nwr::kDistinct];
+        if (nd < 0 || nd > n || (int64_t)ctr[nwr::kKept] > n) return rfail(c, NW_E_STATE, "inconsistent counters");
+        res->n_no_seq = (int64_t)ctr[nwr::kDropped];
+        R->stats[0] = (int64_t)ctr[nwr::kAligned];
+        R->stats[1] = (int64_t)ctr[nwr::kKept];
+        if (nd == 0) return NW_OK;
+
+        // the used slots to the host; the regions in key order
+        std::vector<nwr::Listed> list((size_t)nd);
+        RHIP(c, c->d_list.reserve((size_t)nd));
+        RHIP(c, hipEventRecord(c->ev[0], st));
+        hipLaunchKernelGGL(nwr::nwr_compact_kernel, dim3((unsigned)((slots + nwr::kBlk - 1) / nwr::kBlk)), dim3(nwr::kBlk), 0, st, t,
+                           c->d_list.p, (uint64_t)nd, c->d_ctr.p);
+        RHIP(c, hipGetLastError());
+        RHIP(c, hipEventRecord(c->ev[1], st));
+        RHIP(c, hipMemcpyAsync(list.data(), c->d_list.p, sizeof(nwr::Listed) * (size_t)nd, hipMemcpyDeviceToHost, st));
+        RHIP(c, hipMemcpyAsync(ctr, c->d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+        RHIP(c, hipStreamSynchronize(st));
+        float ms = 0.0f;
+        RHIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        res->kernel_ms += ms;
+        if ((int64_t)ctr[nwr::kListed] != nd) return rfail(c, NW_E_STATE, "inconsistent table");
+        std::vector<nwr_region> key((size_t)nd);
+        int64_t sum = 0;
+        for (int64_t e = 0; e < nd; ++e) {
+            nwr::unpack_key(list[(size_t)e].w0, list[(size_t)e].w1, &key[(size_t)e]);
+            sum += list[(size_t)e].count;
+            if ((uint64_t)list[(size_t)e].slot > t.cap_mask) return rfail(c, NW_E_STATE, "inconsistent table");
+        }
+        if (sum != R->stats[1]) return rfail(c, NW_E_STATE, "inconsistent table");
+        std::vector<int64_t> order((size_t)nd);
+        std::iota(order.begin(), order.end(), 0);
+        std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {      // (the keys are distinct)
+            const nwr_region &p = key[(size_t)x], &q = key[(size_t)y];
+            if (p.ref_id != q.ref_id) return p.ref_id < q.ref_id;
+            if (p.bpstart != q.bpstart) return p.bpstart < q.bpstart;
+            return p.bpend < q.bpend;
+        });
+        if (nd > 0x7FFFFFFF) return rfail(c, NW_E_UNSUPPORTED, "%lld regions", (long long)nd);
+        n_regions = nd;
+        R->regions.resize((size_t)nd);
+        R->n_records.resize((size_t)nd);
+        std::vector<uint32_t> lslot((size_t)nd);
+        std::vector<int32_t> lreg((size_t)nd);
+        int64_t emitted = 0;
+        for (int64_t g = 0; g < nd; ++g) {
+            const size_t e = (size_t)order[(size_t)g];
+            R->regions[(size_t)g] = key[e];
+            R->n_records[(size_t)g] = list[e].count;
+            lslot[(size_t)g] = list[e].slot;
+            const bool emit = (int64_t)list[e].count >= min_reads;
+            lreg[(size_t)g] = emit ? (int32_t)g : -1;
+            emitted += emit;
+        }
+        R->stats[2] = emitted;
+        if (emitted > NWR_MAX_REGIONS)
+            return rfail(c, NW_E_UNSUPPORTED, "%lld regions to emit: at most %d are supported (raise min_reads)",
+                         (long long)emitted, NWR_MAX_REGIONS);
+        if (emitted == 0) return NW_OK;
+        RHIP(c, c->d_lslot.reserve((size_t)nd));
+        RHIP(c, c->d_lreg.reserve((size_t)nd));
+        RHIP(c, c->d_map.reserve(slots));
+        RHIP(c, hipMemcpyAsync(c->d_lslot.p, lslot.data(), sizeof(uint32_t) * (size_t)nd, hipMemcpyHostToDevice, st));
+        RHIP(c, hipMemcpyAsync(c->d_lreg.p, lreg.data(), sizeof(int32_t) * (size_t)nd, hipMemcpyHostToDevice, st));
+        RHIP(c, hipEventRecord(c->ev[0], st));
+        hipLaunchKernelGGL(nwr::nwr_scatter_kernel, dim3((unsigned)((nd + nwr::kBlk - 1) / nwr::kBlk)), dim3(nwr::kBlk), 0, st,
+                           c->d_lslot.p, c->d_lreg.p, nd, t.cap_mask, c->d_map.p);
+        RHIP(c, hipGetLastError());
+        RHIP(c, hipEventRecord(c->ev[1], st));
+        RHIP(c, hipStreamSynchronize(st));
+        RHIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        res->kernel_ms += ms;
+
+        // pass 2: a one-chunk call still has its records in d_data
+        std::vector<int64_t> cursor((size_t)nd + 1);
+        for (const auto& r : ranges) {
+            nwr::Hits h;
+            const int rc2 = emit_chunk(c, bam, r.first, r.second, flags, ranges.size() == 1, nd, &cursor, &h, &res->kernel_ms,
+                                       &res->upload_ms);
+            if (rc2 != NW_OK) return rc2;
+            if (!h.reg.empty()) chunks.push_back(std::move(h));
+        }
+        return NW_OK;
+    }();
+    if (rc != NW_OK) {
+        delete R;
+        res->handle = nullptr;
+        return rc;
+    }
+    merge_chunks(chunks, n_regions, R);
+    res->n_regions = n_regions;
+    res->n_hits = (int64_t)R->h.reg.size();
+    res->n_bytes = R->h.toff.back();
+    return NW_OK;
+}
+
+int nwr_fetch_regions(const nwr_result* res, nwr_region* regions, int64_t* n_records, int64_t stats[4]) {
+    if (!res || !res->handle) return NW_E_INVALID;
+    const nwr::Result* R = (const nwr::Result*)res->handle;
+    if (!R->discovered) return NW_E_STATE;
+    const size_t nr = R->regions.size();
+    if (regions && nr) std::memcpy(regions, R->regions.data(), sizeof(nwr_region) * nr);
+    if (n_records && nr) std::memcpy(n_records, R->n_records.data(), sizeof(int64_t) * nr);
+    if (stats) std::memcpy(stats, R->stats, sizeof R->stats);
     return NW_OK;
 }
 

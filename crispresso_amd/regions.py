@@ -1,13 +1,15 @@
 """BAM records to the reads of every target on the GPU, behind the C ABI of
 ``include/crispr_regions.h``.
 
-Two loops of the reference end here:
+Three loops of the reference end here:
 
 * ``CRISPRessoWGS`` (CRISPResso/CRISPRessoWGSCORE.py:166-221, called at :653-703): per region
   ``samtools view | cut`` into Python, per read a list with one entry per base
   (``get_reference_positions``), ``in`` / ``index`` on it and a slice of sequence and qualities;
 * ``CRISPRessoPooled``, amplicon mode (CRISPRessoPooledCORE.py:870-878): ``samtools view -F 4 |
-  awk`` appends every mapped record to the FASTQ of its reference.
+  awk`` appends every mapped record to the FASTQ of its reference;
+* ``CRISPRessoPooled``, genome mode (CRISPRessoPooledCORE.py:1045-1082): ``samtools view -F 4 | awk |
+  sort | awk`` writes one FASTQ per distinct clip-extended span of the mapped records.
 
 Here the BAM is inflated and validated on the host (crispresso_amd/csrc/nw_bam.cpp), the CIGAR
 walk, the region lookup and the slices run in HBM (crispresso_amd/csrc/nw_regions.hip), and a
@@ -17,6 +19,9 @@ region's reads come back as the packed ``(buf, offsets)`` pair :func:`pooled.ali
 * :func:`records_from_sam`   -- SAM text (what ``samtools view [-h]`` prints) -> :class:`BamRecords`
 * :func:`extract_regions`    -- the reads of every ``(chr_id, bpstart, bpend)`` -> :class:`RegionReads`
 * :func:`demux_by_reference` -- every mapped record to its reference's set -> :class:`RegionReads`
+* :func:`discover_regions`   -- CRISPRessoPooled's genome mode (CRISPRessoPooledCORE.py:1045-1082):
+  every distinct clip-extended span of the mapped records and its reads -> :class:`RegionReads`
+* :func:`region_sequences`   -- the genome's bases of such regions from a FASTA (host side)
 * ``python -m crispresso_amd.regions`` -- one ``.fastq.gz`` per target
 
 The reference's quirk is kept: ``=``, ``X``, ``H`` and ``P`` advance nothing in its walk
@@ -304,17 +309,39 @@ class RegionReads:
             return [self.bam.name(int(r)) for r in self.src[a:b]]
         return [self.bam.name(int(r)) + b"_%d" % (k + 1) for k, r in enumerate(self.src[a:b])]
 
-    def fastq_bytes(self, g: int) -> bytes:
-        """``@name\\nseq\\n+\\nqual\\n`` per read, the text the reference writes."""
+    def _fields(self, g: int):
         (tb, off), (qb, _) = self.reads(g), self.quals(g)
         t, q, o = tb.tobytes(), qb.tobytes(), off.tolist()
-        return b"".join(b"@%s\n%s\n+\n%s\n" % (nm, t[o[k]:o[k + 1]], q[o[k]:o[k + 1]])
-                        for k, nm in enumerate(self.names(g)))
+        return [(nm, t[o[k]:o[k + 1]], q[o[k]:o[k + 1]]) for k, nm in enumerate(self.names(g))]
 
-    def write_fastq_gz(self, g: int, path: str) -> int:
+    def fastq_bytes(self, g: int, order: Optional[Sequence[int]] = None) -> bytes:
+        """``@name\\nseq\\n+\\nqual\\n`` per read, the text the reference writes; ``order`` is a
+        permutation of the target's reads (:meth:`reference_order`), default: as they are."""
+        f = self._fields(g)
+        return b"".join(b"@%s\n%s\n+\n%s\n" % f[k] for k in (range(len(f)) if order is None else order))
+
+    def write_fastq_gz(self, g: int, path: str, order: Optional[Sequence[int]] = None) -> int:
         with gzip.open(path, "wb") as f:
-            f.write(self.fastq_bytes(g))
+            f.write(self.fastq_bytes(g, order))
         return int(self.n_reads[g])
+
+    def strand(self, g: int) -> np.ndarray:
+        """``+`` or ``-`` per read of target ``g`` (uint8), from the records' flags on the host:
+        ``-`` iff ``(flag % 32) >= 16``, as the reference's ``awk`` decides it."""
+        a, b = self._range(g)
+        o = self.bam.offsets[self.src[a:b]]
+        reverse = (self.bam.data[o + 18] & 16) != 0      # (the flag's low byte)
+        return np.where(reverse, np.uint8(ord("-")), np.uint8(ord("+"))).astype(np.uint8)
+
+    def reference_order(self, g: int) -> List[int]:
+        """The permutation of target ``g``'s reads that the reference's ``sort`` leaves inside a
+        region's file: its last-resort comparison of the whole line -- strand, name, sequence and
+        qualities joined by tabs -- bytewise, which is what ``sort`` does under ``LC_ALL=C``
+        (another locale gives the reference another order).  Host side; equal lines keep record
+        order."""
+        s = self.strand(g).tobytes()
+        keys = [b"\t".join((s[k:k + 1],) + f) for k, f in enumerate(self._fields(g))]
+        return sorted(range(len(keys)), key=keys.__getitem__)
 
 
 class GpuRegionExtractor:
@@ -355,18 +382,46 @@ class GpuRegionExtractor:
             msg = lib.nwr_last_error(self._ctx).decode(errors="replace")
             raise RegionsError(f"nwr_extract failed ({rc}): {msg}")
         try:
-            R, H, B = int(res.n_regions), int(res.n_hits), int(res.n_bytes)
-            region_off = np.zeros(R + 1, np.int64)
-            src, st, en = np.empty(H, np.int64), np.empty(H, np.int32), np.empty(H, np.int32)
-            toff, text, qual = np.zeros(H + 1, np.int64), np.empty(B, np.uint8), np.empty(B, np.uint8)
-            rc = lib.nwr_fetch(ctypes.byref(res), _lib.ptr(region_off), _lib.ptr(src), _lib.ptr(st), _lib.ptr(en),
-                               _lib.ptr(toff), _lib.ptr(text), _lib.ptr(qual))
-            if rc != 0:
-                raise RegionsError(f"nwr_fetch failed ({rc})")
+            arrays = self._fetch(res)
         finally:
             lib.nwr_release(ctypes.byref(res))
-        return RegionReads(bam, names, region_off, src, st, en, toff, text, qual, int(res.n_no_seq),
+        return RegionReads(bam, names, *arrays, int(res.n_no_seq),
                            float(res.kernel_ms), float(res.upload_ms), bool(flags & _lib.NWR_BY_REFERENCE))
+
+    def _fetch(self, res):
+        R, H, B = int(res.n_regions), int(res.n_hits), int(res.n_bytes)
+        region_off = np.zeros(R + 1, np.int64)
+        src, st, en = np.empty(H, np.int64), np.empty(H, np.int32), np.empty(H, np.int32)
+        toff, text, qual = np.zeros(H + 1, np.int64), np.empty(B, np.uint8), np.empty(B, np.uint8)
+        rc = self._lib.nwr_fetch(ctypes.byref(res), _lib.ptr(region_off), _lib.ptr(src), _lib.ptr(st), _lib.ptr(en),
+                                 _lib.ptr(toff), _lib.ptr(text), _lib.ptr(qual))
+        if rc != 0:
+            raise RegionsError(f"nwr_fetch failed ({rc})")
+        return region_off, src, st, en, toff, text, qual
+
+    def discover(self, bam: BamRecords, min_reads: int, flags: int) -> RegionReads:
+        lib = self._lib
+        res = _lib.NwrResult()
+        rc = lib.nwr_discover(self._ctx, bam._h, flags, int(min_reads), ctypes.byref(res))
+        if rc != 0:
+            msg = lib.nwr_last_error(self._ctx).decode(errors="replace")
+            raise RegionsError(f"nwr_discover failed ({rc}): {msg}")
+        try:
+            arrays = self._fetch(res)
+            table = np.zeros(int(res.n_regions), REGION_DTYPE)
+            n_records, stats = np.zeros(len(table), np.int64), np.zeros(4, np.int64)
+            rc = lib.nwr_fetch_regions(ctypes.byref(res), _lib.ptr(table) if len(table) else None,
+                                       _lib.ptr(n_records) if len(table) else None, _lib.ptr(stats))
+            if rc != 0:
+                raise RegionsError(f"nwr_fetch_regions failed ({rc})")
+        finally:
+            lib.nwr_release(ctypes.byref(res))
+        regs = [(bam.ref_names[int(r)], int(s), int(e)) for r, s, e in zip(table["ref_id"], table["bpstart"], table["bpend"])]
+        out = RegionReads(bam, ["REGION_%s_%d_%d" % r for r in regs], *arrays, int(res.n_no_seq), float(res.kernel_ms),
+                          float(res.upload_ms), True)
+        out.regions, out.region_table, out.n_records = regs, table, n_records
+        out.n_aligned, out.n_kept, out.n_emitted = int(stats[0]), int(stats[1]), int(stats[2])
+        return out
 
 
 _DEFAULT: Dict[int, GpuRegionExtractor] = {}
@@ -414,6 +469,95 @@ def demux_by_reference(bam: BamRecords, device: int = 0, extractor: Optional[Gpu
     return (extractor or default_extractor(device)).extract(bam, None, list(bam.ref_names), _lib.NWR_BY_REFERENCE)
 
 
+def discover_regions(bam: BamRecords, min_reads: int = 0, eqx_as_match: bool = False, device: int = 0,
+                     extractor: Optional[GpuRegionExtractor] = None) -> RegionReads:
+    """CRISPRessoPooled's genome mode (CRISPRessoPooledCORE.py:1045-1082): every mapped record's
+    clip-extended span ``(chr_id, bpstart, bpend)`` is a region, every distinct span one target
+    with the records that have it, whole, in BAM record order.  The walk and its ``=`` / ``X``
+    quirk are stated in ``include/crispr_regions.h``.
+
+    The targets come in ascending ``(reference index, bpstart, bpend)`` order, compared as numbers;
+    ``target_names[g]`` is ``REGION_<chr>_<bpstart>_<bpend>``, names are plain.  Beside what every
+    :class:`RegionReads` has: ``regions`` (a list of ``(chr_id, bpstart, bpend)``, the name of
+    the reference and two Python ints, which may be zero or negative), ``region_table`` (the same
+    with reference indices, int64 ends), ``n_records`` (int64, the records of every region in the
+    whole BAM), ``n_aligned`` (records with ``flag & 0x904 == 0``, the reference's denominator of
+    ``n_reads_aligned_%``), ``n_kept`` and ``n_emitted``.
+
+    A region with fewer than ``min_reads`` records is reported (name, key, ``n_records``) but
+    its reads are not produced: its range in ``region_offsets`` is empty and ``n_reads`` is 0.
+    The reference runs a region iff ``n_reads > min_reads_to_use_region`` in ``ONLY_GENOME`` mode
+    (pass that value + 1) and iff ``>=`` in ``AMPLICONS_AND_GENOME`` mode (pass it as it is); its
+    default is 1000, the default here emits everything.
+
+    Three deliberate differences from the reference: a record without sequence or qualities is
+    dropped and counted in ``n_no_seq``; a mapped record without a reference (``*``) is dropped,
+    where the reference writes ``REGION_*_0_0``; reads come in record order, not in the order of
+    ``sort``'s whole-line comparison -- :meth:`RegionReads.reference_order` restores that."""
+    flags = _lib.NWR_EQX_AS_MATCH if eqx_as_match else 0
+    return (extractor or default_extractor(device)).discover(bam, min_reads, flags)
+
+
+def _fasta_index(fasta_path: str) -> Dict[str, Tuple[int, int, int, int]]:
+    """name -> (length, offset of the first base, bases per line, bytes per line): the ``.fai``
+    beside the file when there is one, else one pass over the file."""
+    import os
+
+    index: Dict[str, Tuple[int, int, int, int]] = {}
+    if os.path.exists(fasta_path + ".fai"):
+        with open(fasta_path + ".fai") as f:
+            for line in f:
+                c = line.rstrip("\n").split("\t")
+                if len(c) >= 5:
+                    index.setdefault(c[0], (int(c[1]), int(c[2]), int(c[3]), int(c[4])))
+        return index
+    with open(fasta_path, "rb") as f:
+        name, at = None, 0
+        length = start = bases = width = 0
+        for line in f:
+            if line.startswith(b">"):
+                if name is not None:
+                    index.setdefault(name, (length, start, bases, width))
+                name = line[1:].split()[0].decode("latin-1") if line[1:].split() else ""
+                length, start, bases, width = 0, at + len(line), 0, 0
+            elif name is not None:
+                body = line.rstrip(b"\r\n")
+                if bases == 0 and body:
+                    bases, width = len(body), len(line)
+                length += len(body)
+            at += len(line)
+        if name is not None:
+            index.setdefault(name, (length, start, bases, width))
+    return index
+
+
+def region_sequences(fasta_path: str, regions: Sequence[Region]) -> List[str]:
+    """The genome's bases of every ``(chr_id, bpstart, bpend)``: ``[bpstart, bpend)`` 1-based, which
+    is the ``chr:bpstart-(bpend-1)`` that the reference's ``get_region_from_fa`` asks of
+    ``samtools faidx``, as stored (no case change).  Host side, a plain (uncompressed) FASTA whose
+    sequence lines have one width, as ``faidx`` requires; its ``.fai`` is used when present.
+
+    The interval is cut to ``[1, length]``; a region outside it, or on a name the FASTA does not
+    have, gives ``""``.  That cut is this function's choice, not pinned against ``samtools``."""
+    index = _fasta_index(fasta_path)
+    out = []
+    with open(fasta_path, "rb") as f:
+        for r in regions:
+            entry = index.get(str(r[0]))
+            if entry is None:
+                out.append("")
+                continue
+            length, start, bases, width = entry
+            a, b = max(int(r[1]), 1) - 1, min(int(r[2]) - 1, length)      # 0-based [a, b)
+            if b <= a or bases <= 0:
+                out.append("")
+                continue
+            lo, hi = start + a // bases * width + a % bases, start + (b - 1) // bases * width + (b - 1) % bases + 1
+            f.seek(lo)
+            out.append(f.read(hi - lo).replace(b"\n", b"").replace(b"\r", b"").decode("latin-1"))
+    return out
+
+
 def main(argv=None) -> int:
     import argparse
     import os
@@ -424,14 +568,40 @@ def main(argv=None) -> int:
     g = p.add_mutually_exclusive_group(required=True)
     g.add_argument("--regions", help="region file: chr_id, bpstart, bpend[, name], tab-separated")
     g.add_argument("--by-reference", action="store_true", help="one read set per reference of the BAM")
+    g.add_argument("--discover", action="store_true",
+                   help="one read set per distinct clip-extended span of the mapped records (CRISPRessoPooled's genome mode)")
     p.add_argument("--eqx-as-match", action="store_true", help="treat the CIGAR operations = and X as M")
+    p.add_argument("--min-reads", type=int, default=0, help="with --discover: write only regions with at least N reads")
+    p.add_argument("--genome", help="with --discover: a plain FASTA; regions.tsv gets the regions' sequences")
+    p.add_argument("--reference-order", action="store_true",
+                   help="with --discover: reads in the order the reference's sort leaves them (C locale)")
     p.add_argument("--out", required=True, help="output directory")
     p.add_argument("--device", type=int, default=0)
     args = p.parse_args(argv)
-    for f in (args.bam, args.regions):
+    if not args.discover and (args.min_reads or args.genome or args.reference_order):
+        p.error("--min-reads, --genome and --reference-order go with --discover")
+    if args.min_reads < 0:
+        p.error("--min-reads must not be negative")
+    for f in (args.bam, args.regions, args.genome):
         if f and not os.path.exists(f):
             p.error(f"cannot open {f}")
     bam = read_bam(args.bam)
+    if args.discover:
+        res = discover_regions(bam, args.min_reads, args.eqx_as_match, args.device)
+        os.makedirs(args.out, exist_ok=True)
+        seqs = region_sequences(args.genome, res.regions) if args.genome else None
+        with open(os.path.join(args.out, "regions.tsv"), "w") as tsv:
+            tsv.write("\t".join(["chr_id", "bpstart", "bpend", "n_reads", "n_reads_aligned_%"] + (["sequence"] if seqs is not None else []))
+                      + "\n")
+            for t, (name, (chr_id, s, e)) in enumerate(zip(res.target_names, res.regions)):
+                n = int(res.n_records[t])
+                pct = "%.6g" % (n / float(res.n_aligned) * 100.0) if res.n_aligned else "NA"
+                tsv.write("\t".join(map(str, [chr_id, s, e, n, pct] + ([seqs[t]] if seqs is not None else []))) + "\n")
+                if n >= args.min_reads:
+                    order = res.reference_order(t) if args.reference_order else None
+                    res.write_fastq_gz(t, os.path.join(args.out, name.replace(os.sep, "_") + ".fastq.gz"), order)
+                    print(f"{name}\t{n}")
+        return 0
     if args.by_reference:
         res = demux_by_reference(bam, args.device)
     else:

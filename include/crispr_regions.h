@@ -1,5 +1,6 @@
 /* crispr_regions.h -- C ABI of the MI355X BAM-to-target reads: a BAM's records become the reads
- * of every target region (CRISPRessoWGS) or of every reference (CRISPRessoPooled, amplicon mode).
+ * of every target region (CRISPRessoWGS), of every reference (CRISPRessoPooled, amplicon mode) or
+ * of every region the records themselves span (CRISPRessoPooled, genome mode: nwr_discover below).
  *
  * Replaces the per-read loop of write_trimmed_fastq / get_reference_positions
  * (CRISPResso/CRISPRessoWGSCORE.py:166-221) and the `samtools view -F 4 | awk` demultiplex of
@@ -104,6 +105,46 @@ int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64
 int nwr_fetch(const nwr_result* res, int64_t* region_offsets, int64_t* src, int32_t* st, int32_t* en,
               int64_t* text_offsets, uint8_t* text, uint8_t* quals);
 void nwr_release(nwr_result* res);
+
+/* CRISPRessoPooled's genome mode (CRISPRessoPooledCORE.py:1045-1082: `samtools view -F 4 | awk |
+ * sort | awk`): nobody names the regions, the records do.  A record takes part iff flag & 4 == 0,
+ * ref_id >= 0 and it has a sequence and qualities.  Its span: pos is BAM's pos + 1, bpstart =
+ * bpend = pos, then in the order of the ops
+ *   S           bpstart -= len while bpend == pos (nothing has advanced yet, whatever H or I came
+ *               before; every leading S does so), else bpend += len
+ *   I, H        nothing
+ *   M, D, N, P  bpend += len
+ *   =, X and the op codes 9-15: the reference splits the CIGAR text on [MIDNSHP], so a maximal
+ *               run of these ops and the op after it are one op to it: of the kind of the op
+ *               after the run (M at the CIGAR's end), of the length of the run's first op; the
+ *               other lengths are lost.  5=3X2M at 100 gives 100..105, 10M5= 100..115, 3S5=2M
+ *               97..105.  With NWR_EQX_AS_MATCH, = and X are M and the codes 9-15 are nothing.
+ * No CIGAR gives (pos, pos); bpstart may be zero or negative.  A region is a distinct (ref_id,
+ * bpstart, bpend); the result's regions come in ascending (ref_id, bpstart, bpend), compared as
+ * numbers, a region's reads in record order, whole (st = 0, en = l_seq), bases as stored.
+ *
+ * Three deliberate differences from the reference: (1) a record without sequence or qualities is
+ * dropped and counted in n_no_seq (the reference writes its "*"); (2) a mapped record with ref_id
+ * -1 is dropped (the reference writes a REGION_*_0_0 file for it); (3) the reads of a region come
+ * in record order, where the reference has the order of `sort`'s last-resort comparison of whole
+ * lines (strand, name, sequence, qualities, bytewise under the C locale, different under others);
+ * crispresso_amd/regions.py restores that order on the host on request.
+ *
+ * min_reads: a region with at least min_reads records in the whole call has its reads emitted;
+ * any other region is still reported by nwr_fetch_regions, with an empty range in
+ * region_offsets (min_reads <= 0 emits all).  The only flag is NWR_EQX_AS_MATCH.  At most 2^30
+ * records in a call and NWR_MAX_REGIONS regions *emitted* (any number reported), and the chunk
+ * limits of nwr_extract, else NW_E_UNSUPPORTED; a full table (which the sizing rules out) is
+ * NW_E_STATE.  CRISPR_NWR_HASH_BITS=k, read at nwr_create, keeps the low k bits of the key's hash,
+ * so that tests reach long probe chains and distinct keys under one hash on small inputs.  The
+ * result is served by nwr_fetch and nwr_release as above, and is a function of the input alone. */
+int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_reads, nwr_result* res);
+
+/* After nwr_discover (NW_E_STATE after nwr_extract): regions [n_regions] the keys in result order,
+ * n_records [n_regions] the records of each in the whole call, emitted or not; stats: n_aligned
+ * (records with flag & 0x904 == 0, the reference's get_n_aligned_bam), the kept records, the
+ * emitted regions, 0 (reserved).  Any pointer may be NULL. */
+int nwr_fetch_regions(const nwr_result* res, nwr_region* regions, int64_t* n_records, int64_t stats[4]);
 
 #ifdef __cplusplus
 }
