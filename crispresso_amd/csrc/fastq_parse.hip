@@ -47,6 +47,7 @@
 
 #include "../../include/crispr_ingest.h"
 #include "gz_inflate.h"
+#include "host_dev.h"
 #include "host_pool.h"
 #include "ingest_device.h"
 
@@ -341,28 +342,13 @@ int fail(int code, const std::string& msg) {
 }
 
 // a call's scratch arrays and events: released when it goes out of scope
-struct Scratch {
-    std::vector<void*> bufs;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Scratch() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        for (void* p : bufs) (void)hipFree(p);
-    }
-    void* dev(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return p;
-    }
-    bool begin() { return hipEventRecord(e0, nullptr) == hipSuccess; }
+struct Scratch : hd::DevBag {
     // adds what ran since begin() to *ms
     bool end(float* ms) {
         float d = 0.0f;
-        const bool ok = hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess &&
-                        hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&d, e0, e1) == hipSuccess;
-        if (ok) *ms += d;
-        return ok;
+        if (!elapsed(&d)) return false;
+        *ms += d;
+        return true;
     }
 };
 
@@ -396,7 +382,6 @@ int parse(const char* who, int device, const uint8_t* text, int64_t bytes, float
         return 0;
     }
     Scratch S;
-    if (hipEventCreate(&S.e0) != hipSuccess || hipEventCreate(&S.e1) != hipSuccess) return hip_fail();
     const uint32_t T = (uint32_t)bytes;
     const int64_t chunks = ((int64_t)bytes + 15) / 16, blocks = (chunks + kBlk - 1) / kBlk;
     uint8_t* d_text = (uint8_t*)S.dev((size_t)(16 * chunks) + 16);

@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "flash_device.h"
+#include "host_dev.h"
 
 namespace nwf {
 
@@ -252,40 +253,27 @@ extern "C" int nwf_merge_batch(int device, const nwf_params* params, const uint8
     }
     if (lmax > kMaxLen) return fail(-3, "nwf_merge_batch: reads longer than 4096 bases are not supported");
     if (hipSetDevice(device) != hipSuccess) return fail(-4, "nwf_merge_batch: hipSetDevice failed");
-    std::vector<void*> bufs;
-    auto dev = [&](size_t bytes) -> void* {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return p;
-    };
-    auto cleanup = [&]() {
-        for (void* p : bufs) (void)hipFree(p);
-    };
+    hd::DevBag bag;
     Args a{};
     // + 8 bytes of slack after each buffer (none is read, but a reader never runs off an allocation)
-    uint8_t* d_s1 = (uint8_t*)dev(t1 + 8);
-    uint8_t* d_q1 = (uint8_t*)dev(t1 + 8);
-    uint8_t* d_s2 = (uint8_t*)dev(t2 + 8);
-    uint8_t* d_q2 = (uint8_t*)dev(t2 + 8);
-    int64_t* d_o1 = (int64_t*)dev(sizeof(int64_t) * (n + 1));
-    int64_t* d_o2 = (int64_t*)dev(sizeof(int64_t) * (n + 1));
-    uint8_t* d_os = (uint8_t*)dev(t1 + t2 + 8);
-    uint8_t* d_oq = (uint8_t*)dev(t1 + t2 + 8);
-    int32_t* d_len = (int32_t*)dev(sizeof(int32_t) * n);
-    int32_t* d_flg = (int32_t*)dev(sizeof(int32_t) * n);
-    if (!d_s1 || !d_q1 || !d_s2 || !d_q2 || !d_o1 || !d_o2 || !d_os || !d_oq || !d_len || !d_flg) {
-        cleanup();
+    uint8_t* d_s1 = (uint8_t*)bag.dev(t1 + 8);
+    uint8_t* d_q1 = (uint8_t*)bag.dev(t1 + 8);
+    uint8_t* d_s2 = (uint8_t*)bag.dev(t2 + 8);
+    uint8_t* d_q2 = (uint8_t*)bag.dev(t2 + 8);
+    int64_t* d_o1 = (int64_t*)bag.dev(sizeof(int64_t) * (n + 1));
+    int64_t* d_o2 = (int64_t*)bag.dev(sizeof(int64_t) * (n + 1));
+    uint8_t* d_os = (uint8_t*)bag.dev(t1 + t2 + 8);
+    uint8_t* d_oq = (uint8_t*)bag.dev(t1 + t2 + 8);
+    int32_t* d_len = (int32_t*)bag.dev(sizeof(int32_t) * n);
+    int32_t* d_flg = (int32_t*)bag.dev(sizeof(int32_t) * n);
+    if (!d_s1 || !d_q1 || !d_s2 || !d_q2 || !d_o1 || !d_o2 || !d_os || !d_oq || !d_len || !d_flg)
         return fail(-4, "nwf_merge_batch: hipMalloc failed");
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     bool ok = hipMemcpy(d_s1, seq1, t1, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_q1, qual1, t1, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_s2, seq2, t2, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_q2, qual2, t2, hipMemcpyHostToDevice) == hipSuccess &&
               hipMemcpy(d_o1, off1, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d_o2, off2, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess &&
-              hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
+              hipMemcpy(d_o2, off2, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess;
     if (ok) {
         a.seq1 = d_s1;
         a.qual1 = d_q1;
@@ -305,21 +293,16 @@ extern "C" int nwf_merge_batch(int device, const nwf_params* params, const uint8
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
             dev_cus = prop.multiProcessorCount;
         const int64_t grid = std::max<int64_t>(1, std::min<int64_t>((n + kWpb - 1) / kWpb, (int64_t)dev_cus * 16));
-        ok = hipEventRecord(e0, nullptr) == hipSuccess;
+        ok = bag.begin();
         if (ok) {
             launch_merge(a, (unsigned)grid, lds, false);
-            ok = hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess &&
-                 hipEventSynchronize(e1) == hipSuccess;
+            ok = bag.elapsed(kernel_ms);
         }
-        if (ok && kernel_ms) ok = hipEventElapsedTime(kernel_ms, e0, e1) == hipSuccess;
         ok = ok && hipMemcpy(out_len, d_len, sizeof(int32_t) * n, hipMemcpyDeviceToHost) == hipSuccess &&
              hipMemcpy(out_flags, d_flg, sizeof(int32_t) * n, hipMemcpyDeviceToHost) == hipSuccess &&
              (!out_seq || hipMemcpy(out_seq, d_os, t1 + t2, hipMemcpyDeviceToHost) == hipSuccess) &&
              (!out_qual || hipMemcpy(out_qual, d_oq, t1 + t2, hipMemcpyDeviceToHost) == hipSuccess);
     }
-    if (e0) (void)hipEventDestroy(e0);
-    if (e1) (void)hipEventDestroy(e1);
-    cleanup();
     if (!ok) return fail(-4, std::string("nwf_merge_batch: HIP error: ") + hipGetErrorString(hipGetLastError()));
     return 0;
 }

@@ -470,7 +470,7 @@ int run_call(const char* who, nw_ctx* ctx, const nwp_params* params, nwt::Progra
         fa.n = n, fa.paired = paired;
         fa.min_avg = params->min_avg_quality, fa.min_single = params->min_single_quality;
         fa.live = d_live;
-        if (hipEventRecord(b.e0, nullptr) != hipSuccess) return hip_fail();
+        if (!b.begin()) return hip_fail();
         hipLaunchKernelGGL(nwp_filter_kernel, dim3(b.grid(n, kWpb)), dim3(64 * kWpb), 0, nullptr, fa);
         if (!b.elapsed(ms + NWP_MS_FILTER)) return hip_fail();
     }
@@ -484,7 +484,7 @@ int run_call(const char* who, nw_ctx* ctx, const nwp_params* params, nwt::Progra
         nwf::set_params(ma, &params->flash, lmax);
         ma.start1 = d_win[0], ma.keep1 = d_win[1], ma.start2 = d_win[2], ma.keep2 = d_win[3];
         ma.live = d_live;
-        if (hipEventRecord(b.e0, nullptr) != hipSuccess) return hip_fail();
+        if (!b.begin()) return hip_fail();
         nwf::launch_merge(ma, b.grid(n, nwf::kWpb), nwf::merge_lds(ma), trim || filter);
         if (!b.elapsed(ms + NWP_MS_MERGE)) return hip_fail();
     }
@@ -496,8 +496,7 @@ int run_call(const char* who, nw_ctx* ctx, const nwp_params* params, nwt::Progra
     pa.s.live = d_live;
     pa.s.n = n;
     float ms_a = 0.0f, ms_b = 0.0f;
-    if (hipMemsetAsync(pa.counters, 0, sizeof(unsigned long long) * kCounters, nullptr) != hipSuccess ||
-        hipEventRecord(b.e0, nullptr) != hipSuccess)
+    if (hipMemsetAsync(pa.counters, 0, sizeof(unsigned long long) * kCounters, nullptr) != hipSuccess || !b.begin())
         return hip_fail();
     hipLaunchKernelGGL(nwp_count_kernel, dim3((unsigned)blocks), dim3(kBlk), 0, nullptr, pa);
     hipLaunchKernelGGL(nwp_scan_kernel, dim3(1), dim3(kScanBlk), 0, nullptr, pa);
@@ -529,7 +528,7 @@ int run_call(const char* who, nw_ctx* ctx, const nwp_params* params, nwt::Progra
     if (!pa.offsets || !pa.lens || !pa.src || !pa.gbase || !pa.text || (params->want_quals && !pa.quals) ||
         !pa.exc_pos || !pa.exc_byte || !pa.words)
         return bail(fail(-4, me + "hipMalloc failed"));
-    if (hipEventRecord(b.e0, nullptr) != hipSuccess) return hip_fail();
+    if (!b.begin()) return hip_fail();
     hipLaunchKernelGGL(nwp_scatter_kernel, dim3((unsigned)blocks), dim3(kBlk), 0, nullptr, pa);
     if (nwords > 0)
         hipLaunchKernelGGL(nwp_words_kernel, dim3((unsigned)((nwords + 255) / 256)), dim3(256), 0, nullptr, pa.text,
@@ -628,6 +627,6 @@ extern "C" int nwp_prepare_records(nw_ctx* ctx, const nwp_params* params, const 
         b.s2 = (uint8_t*)b.dev(8), b.q2 = (uint8_t*)b.dev(8), b.o2 = (int64_t*)b.dev(sizeof(int64_t));
         if (!b.s2 || !b.q2 || !b.o2) return bail(fail(-4, "nwp_prepare_records: hipMalloc failed"));
     }
-    if (!b.begin(h->device)) return hip_fail();
+    b.set_launch_cap(h->device);
     return run_call(who, ctx, params, P, paired, n, (int)lmax, t[0], t[1], out);
 }

@@ -21,7 +21,6 @@
 
 #include <algorithm>
 #include <atomic>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -30,24 +29,20 @@
 #include <utility>
 #include <vector>
 
+#include "group_device.h"
 #include "host_pool.h"
 #include "nwa_device.h"
 
 namespace nwa {
 
-constexpr uint64_t kPoly = 0x9E3779B97F4A7C15ull;     // odd: a one-dword difference never cancels
-constexpr uint64_t kLenMul = 0xC2B2AE3D27D4EB4Full;
+using grp::fmix64;
+using grp::kLenMul;
+using grp::kPoly;
+using grp::load_dword;
+using grp::shfl_xor64;
+
 constexpr uint64_t kTagMul = 0x165667B19E3779F9ull;
 constexpr int kTile = 2048;                            // flags per block of the scan (256 threads x 8)
-
-__host__ __device__ inline uint64_t fmix64(uint64_t h) {
-    h ^= h >> 33;
-    h *= 0xFF51AFD7ED558CCDull;
-    h ^= h >> 33;
-    h *= 0xC4CEB9FE1A85EC53ull;
-    h ^= h >> 33;
-    return h;
-}
 
 // The hash of a read from the sum of its dword terms: length and tag mixed in, cut to the
 // low `bits` bits (CRISPR_NWA_HASH_BITS), never 0.
@@ -83,32 +78,6 @@ struct Args {
     int32_t* gor;              // [n]
 };
 
-// Dword k of the read at p (L bytes; 4k < L): bytes 4k .. 4k + 3, those at or past L as zero.
-// Aligned loads only, and only of words that hold a byte of the read.
-__device__ inline uint32_t read_dword(const uint8_t* p, int64_t k, int64_t L) {
-    const uintptr_t a = (uintptr_t)p + 4 * (uintptr_t)k;
-    const unsigned m = (unsigned)(a & 3);
-    const uint32_t* w = reinterpret_cast<const uint32_t*>(a - m);
-    const int64_t left = L - 4 * k;
-    const int nb = left < 4 ? (int)left : 4;
-    uint32_t v = w[0] >> (8 * m);
-    if (m && nb > 4 - (int)m) v |= w[1] << (32 - 8 * m);
-    if (nb < 4) v &= (1u << (8 * nb)) - 1u;
-    return v;
-}
-
-__device__ inline uint64_t shfl64(uint64_t v, int src) {
-    const int lo = __shfl((int)(uint32_t)v, src, 64);
-    const int hi = __shfl((int)(uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
-}
-
-__device__ inline uint64_t shfl_xor64(uint64_t v, int mask) {
-    const int lo = __shfl_xor((int)(uint32_t)v, mask, 64);
-    const int hi = __shfl_xor((int)(uint32_t)(v >> 32), mask, 64);
-    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
-}
-
 __global__ __launch_bounds__(256) void hash_kernel(Args a) {
     const int lane = threadIdx.x & 63;
     const int64_t wave = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -126,7 +95,7 @@ __global__ __launch_bounds__(256) void hash_kernel(Args a) {
         const int64_t nd = (L + 3) >> 2;
         uint64_t acc = 0, pw = p1;
         for (int64_t k = lane; k < nd; k += 64) {
-            acc += (uint64_t)read_dword(p, k, L) * pw;
+            acc += (uint64_t)load_dword(p, k, L) * pw;
             pw *= p64;
         }
         for (int o = 32; o > 0; o >>= 1) acc += shfl_xor64(acc, o);
@@ -135,46 +104,16 @@ __global__ __launch_bounds__(256) void hash_kernel(Args a) {
 }
 
 __global__ __launch_bounds__(256) void insert_kernel(Args a) {
-    const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
     const uint64_t h = r < a.n ? a.hash[r] : 0;
     // the lanes that share a hash elect the lowest of them (the smallest read index)
-    bool done = h == 0;
-    int lead = lane;
-    uint32_t cnt = 0;
-    for (;;) {
-        const unsigned long long act = __ballot(!done);
-        if (!act) break;
-        const int l0 = __ffsll((long long)act) - 1;
-        const uint64_t hl = shfl64(h, l0);
-        const bool mine = !done && h == hl;
-        const unsigned long long same = __ballot(mine);
-        if (mine) {
-            done = true;
-            lead = l0;
-            if (lane == l0) cnt = (uint32_t)__popcll(same);
-        }
-    }
+    int lead;
+    const uint32_t cnt = grp::wave_elect(h, h != 0, &lead);
     uint32_t found = 0;
     if (cnt) {
-        uint64_t s = (h * kPoly) >> a.shift;
-        bool ok = false;
-        for (uint64_t probe = 0; probe <= a.cap_mask; ++probe) {      // bounded by the table size
-            unsigned long long k = __hip_atomic_load(&a.key[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (k == 0) k = atomicCAS(&a.key[s], 0ull, (unsigned long long)h);
-            if (k == 0 || k == h) {
-                atomicMin(&a.first[s], (uint32_t)r);
-                atomicAdd(&a.count[s], cnt);
-                ok = true;
-                break;
-            }
-            s = (s + 1) & a.cap_mask;
-        }
-        if (!ok) {
-            a.counters[2] = 1;      // a full table: cannot happen at load <= 1/2; the host reports it
-            s = 0;
-        }
-        found = (uint32_t)s;
+        const uint64_t s = grp::claim_slot(a.key, a.first, a.count, h, (uint32_t)r, cnt, a.shift, a.cap_mask);
+        if (s == grp::kNoSlot) a.counters[2] = 1;      // a full table: cannot happen at load <= 1/2; the host reports it
+        else found = (uint32_t)s;                      // (slot 0 otherwise)
     }
     found = (uint32_t)__shfl((int)found, lead, 64);
     if (h != 0) a.slot[r] = found;
@@ -202,7 +141,7 @@ __global__ __launch_bounds__(256) void verify_kernel(Args a) {
             const uint8_t* p = a.reads + (o0 - a.bias);
             const uint8_t* q = a.reads + (g0 - a.bias);
             const int64_t nd = (L + 3) >> 2;
-            for (int64_t k = lane; k < nd; k += 64) diff |= read_dword(p, k, L) != read_dword(q, k, L);
+            for (int64_t k = lane; k < nd; k += 64) diff |= load_dword(p, k, L) != load_dword(q, k, L);
         }
         if (__ballot(diff) && lane == 0) a.coll[atomicAdd(&a.counters[1], 1u)] = (uint32_t)r;
     }
@@ -292,7 +231,7 @@ __global__ __launch_bounds__(256) void coll_info_kernel(Args a, const uint32_t* 
 
 namespace {
 
-using nwa::afail;
+using hd::fail;
 
 // Groups of the collided reads (sorted by read index) by (tag, bytes), in order of first
 // appearance: grp[i] = the group of collided read i, gfirst / gcount per group.
@@ -334,52 +273,16 @@ uint64_t host_hash(const unsigned char* p, int64_t n, int32_t tag) {
 extern "C" {
 
 int nwa_create(int device, nwa_ctx** out) {
-    if (!out) return NW_E_INVALID;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return NW_E_HIP;
-    nwa_ctx* c = new nwa_ctx();
-    c->device = device;
-    bool ok = hipSetDevice(device) == hipSuccess &&
-              hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; ok && i < 5; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
-    if (!ok) {
-        nwa_destroy(c);
-        return NW_E_HIP;
-    }
+    const int rc = hd::create_context(device, nwa::kEvents, out);
+    if (rc != NW_OK) return rc;
+    nwa_ctx* c = *out;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->num_cus = prop.multiProcessorCount;
-    if (const char* e = std::getenv("CRISPR_NWA_HASH_BITS")) c->hash_bits = std::max(0, std::min(64, std::atoi(e)));
-    *out = c;
+    c->hash_bits = grp::env_hash_bits("CRISPR_NWA_HASH_BITS");
     return NW_OK;
 }
 
-void nwa_destroy(nwa_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    c->d_keep.release();
-    c->d_is_first.release();
-    c->d_tag.release();
-    c->d_gor.release();
-    c->d_hash.release();
-    c->d_key.release();
-    c->d_slot.release();
-    c->d_first.release();
-    c->d_count.release();
-    c->d_gid.release();
-    c->d_coll.release();
-    c->d_counters.release();
-    c->d_tile_sum.release();
-    c->d_tile_off.release();
-    c->d_gfirst.release();
-    c->d_gcount.release();
-    c->d_info.release();
-    nwa::windows_release(c);
-    for (hipEvent_t e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+void nwa_destroy(nwa_ctx* c) { hd::destroy_context(c); }
 
 const char* nwa_last_error(const nwa_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
@@ -397,10 +300,10 @@ int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offset
                      const uint8_t* keep, const int32_t* tag, int64_t* first, int64_t* count, int64_t cap,
                      int32_t* group_of_read, int64_t* n_groups, float* kernel_ms) {
     if (!c) return NW_E_INVALID;
-    if (n < 0 || n > 0x7FFFFFFFll) return afail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
+    if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
     if (!n_groups || cap < 0 || (cap > 0 && (!first || !count)))
-        return afail(c, NW_E_INVALID, "null output array");
-    if (n > 0 && (!d_reads || !d_offsets)) return afail(c, NW_E_INVALID, "null device array");
+        return fail(c, NW_E_INVALID, "null output array");
+    if (n > 0 && (!d_reads || !d_offsets)) return fail(c, NW_E_INVALID, "null device array");
     c->collided = 0;
     std::fill(c->phase_ms, c->phase_ms + 4, 0.0f);
     if (kernel_ms) *kernel_ms = 0.0f;
@@ -414,33 +317,32 @@ int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offset
         if (group_of_read) std::fill(group_of_read, group_of_read + n, -1);
         return NW_OK;
     }
-    AHIP(c, hipSetDevice(c->device));
-    int log2cap = 10;
-    while (((int64_t)1 << log2cap) < 2 * kept) ++log2cap;
-    const size_t slots = (size_t)1 << log2cap;
+    HIP_TRY(c, hipSetDevice(c->device));
+    const grp::TableGeometry tg = grp::table_geometry(kept, c->hash_bits);
+    const size_t slots = tg.slots;
     const int64_t tiles = (n + nwa::kTile - 1) / nwa::kTile;
     const size_t padded = (size_t)tiles * nwa::kTile;
-    AHIP(c, c->d_hash.reserve((size_t)n));
-    AHIP(c, c->d_slot.reserve((size_t)n));
-    AHIP(c, c->d_is_first.reserve(padded));
-    AHIP(c, c->d_key.reserve(slots));
-    AHIP(c, c->d_first.reserve(slots));
-    AHIP(c, c->d_count.reserve(slots));
-    AHIP(c, c->d_gid.reserve(slots));
-    AHIP(c, c->d_coll.reserve((size_t)kept));
-    AHIP(c, c->d_counters.reserve(4));
-    AHIP(c, c->d_tile_sum.reserve((size_t)tiles));
-    AHIP(c, c->d_tile_off.reserve((size_t)tiles));
-    AHIP(c, c->d_gfirst.reserve((size_t)kept));
-    AHIP(c, c->d_gcount.reserve((size_t)kept));
-    AHIP(c, c->d_gor.reserve((size_t)n));
+    HIP_TRY(c, c->d_hash.reserve((size_t)n));
+    HIP_TRY(c, c->d_slot.reserve((size_t)n));
+    HIP_TRY(c, c->d_is_first.reserve(padded));
+    HIP_TRY(c, c->d_key.reserve(slots));
+    HIP_TRY(c, c->d_first.reserve(slots));
+    HIP_TRY(c, c->d_count.reserve(slots));
+    HIP_TRY(c, c->d_gid.reserve(slots));
+    HIP_TRY(c, c->d_coll.reserve((size_t)kept));
+    HIP_TRY(c, c->d_counters.reserve(4));
+    HIP_TRY(c, c->d_tile_sum.reserve((size_t)tiles));
+    HIP_TRY(c, c->d_tile_off.reserve((size_t)tiles));
+    HIP_TRY(c, c->d_gfirst.reserve((size_t)kept));
+    HIP_TRY(c, c->d_gcount.reserve((size_t)kept));
+    HIP_TRY(c, c->d_gor.reserve((size_t)n));
     if (keep) {
-        AHIP(c, c->d_keep.reserve((size_t)n));
-        AHIP(c, hipMemcpy(c->d_keep.p, keep, (size_t)n, hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_keep.reserve((size_t)n));
+        HIP_TRY(c, hipMemcpy(c->d_keep.p, keep, (size_t)n, hipMemcpyHostToDevice));
     }
     if (tag) {
-        AHIP(c, c->d_tag.reserve((size_t)n));
-        AHIP(c, hipMemcpy(c->d_tag.p, tag, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_tag.reserve((size_t)n));
+        HIP_TRY(c, hipMemcpy(c->d_tag.p, tag, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
     }
     nwa::Args a;
     a.reads = d_reads;
@@ -456,9 +358,9 @@ int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offset
     a.first = c->d_first.p;
     a.count = c->d_count.p;
     a.gid = c->d_gid.p;
-    a.cap_mask = (uint64_t)slots - 1;
-    a.shift = 64 - log2cap;
-    a.hash_mask = c->hash_bits >= 64 ? ~0ull : (((uint64_t)1 << c->hash_bits) - 1);
+    a.cap_mask = tg.cap_mask;
+    a.shift = tg.shift;
+    a.hash_mask = tg.hash_mask;
     a.coll = c->d_coll.p;
     a.counters = c->d_counters.p;
     a.tile_sum = c->d_tile_sum.p;
@@ -468,68 +370,68 @@ int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offset
     a.gor = c->d_gor.p;
 
     hipStream_t st = c->stream;
-    AHIP(c, hipMemsetAsync(a.key, 0, sizeof(unsigned long long) * slots, st));
-    AHIP(c, hipMemsetAsync(a.first, 0xFF, sizeof(uint32_t) * slots, st));
-    AHIP(c, hipMemsetAsync(a.count, 0, sizeof(uint32_t) * slots, st));
-    AHIP(c, hipMemsetAsync(a.is_first, 0, padded, st));
-    AHIP(c, hipMemsetAsync(a.counters, 0, sizeof(uint32_t) * 4, st));
+    HIP_TRY(c, hipMemsetAsync(a.key, 0, sizeof(unsigned long long) * slots, st));
+    HIP_TRY(c, hipMemsetAsync(a.first, 0xFF, sizeof(uint32_t) * slots, st));
+    HIP_TRY(c, hipMemsetAsync(a.count, 0, sizeof(uint32_t) * slots, st));
+    HIP_TRY(c, hipMemsetAsync(a.is_first, 0, padded, st));
+    HIP_TRY(c, hipMemsetAsync(a.counters, 0, sizeof(uint32_t) * 4, st));
     const unsigned wave_grid = (unsigned)std::min<int64_t>((n + 3) / 4, (int64_t)16 * c->num_cus);
     const unsigned lane_grid = (unsigned)((n + 255) / 256);
-    AHIP(c, hipEventRecord(c->ev[0], st));
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
     hipLaunchKernelGGL(nwa::hash_kernel, dim3(wave_grid), dim3(256), 0, st, a);
-    AHIP(c, hipGetLastError());
-    AHIP(c, hipEventRecord(c->ev[1], st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[1], st));
     hipLaunchKernelGGL(nwa::insert_kernel, dim3(lane_grid), dim3(256), 0, st, a);
-    AHIP(c, hipGetLastError());
-    AHIP(c, hipEventRecord(c->ev[2], st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[2], st));
     hipLaunchKernelGGL(nwa::verify_kernel, dim3(wave_grid), dim3(256), 0, st, a);
-    AHIP(c, hipGetLastError());
-    AHIP(c, hipEventRecord(c->ev[3], st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[3], st));
     hipLaunchKernelGGL(nwa::tile_sum_kernel, dim3((unsigned)tiles), dim3(256), 0, st, a);
-    AHIP(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(nwa::tile_scan_kernel, dim3(1), dim3(1024), 0, st, a, tiles);
-    AHIP(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(nwa::emit_kernel, dim3((unsigned)tiles), dim3(256), 0, st, a);
-    AHIP(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(nwa::assign_kernel, dim3(lane_grid), dim3(256), 0, st, a);
-    AHIP(c, hipGetLastError());
-    AHIP(c, hipEventRecord(c->ev[4], st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[4], st));
     uint32_t ctr[4] = {0, 0, 0, 0};
-    AHIP(c, hipMemcpyAsync(ctr, a.counters, sizeof ctr, hipMemcpyDeviceToHost, st));
-    AHIP(c, hipStreamSynchronize(st));
-    for (int i = 0; i < 4; ++i) AHIP(c, hipEventElapsedTime(&c->phase_ms[i], c->ev[i], c->ev[i + 1]));
-    if (kernel_ms) AHIP(c, hipEventElapsedTime(kernel_ms, c->ev[0], c->ev[4]));
-    if (ctr[2]) return afail(c, NW_E_STATE, "the hash table's probe bound was reached (%zu slots, %lld reads)", slots,
-                             (long long)kept);
+    HIP_TRY(c, hipMemcpyAsync(ctr, a.counters, sizeof ctr, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    for (int i = 0; i < 4; ++i) HIP_TRY(c, hipEventElapsedTime(&c->phase_ms[i], c->ev[i], c->ev[i + 1]));
+    if (kernel_ms) HIP_TRY(c, hipEventElapsedTime(kernel_ms, c->ev[0], c->ev[4]));
+    if (ctr[2]) return fail(c, NW_E_STATE, "the hash table's probe bound was reached (%zu slots, %lld reads)", slots,
+                            (long long)kept);
     const int64_t ng_dev = ctr[0], nc = ctr[1];
-    if (ng_dev > kept || nc > kept) return afail(c, NW_E_STATE, "inconsistent group count");
+    if (ng_dev > kept || nc > kept) return fail(c, NW_E_STATE, "inconsistent group count");
 
     // the collided reads (equal hashes, different bytes): grouped exactly here
     std::vector<uint32_t> coll((size_t)nc);
     std::vector<nwa::CollInfo> info((size_t)nc);
     std::vector<int64_t> cgrp, cg_count, cg_first;
     if (nc > 0) {
-        AHIP(c, hipMemcpy(coll.data(), a.coll, sizeof(uint32_t) * (size_t)nc, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(coll.data(), a.coll, sizeof(uint32_t) * (size_t)nc, hipMemcpyDeviceToHost));
         std::sort(coll.begin(), coll.end());
-        AHIP(c, hipMemcpy(a.coll, coll.data(), sizeof(uint32_t) * (size_t)nc, hipMemcpyHostToDevice));
-        AHIP(c, c->d_info.reserve((size_t)nc));
+        HIP_TRY(c, hipMemcpy(a.coll, coll.data(), sizeof(uint32_t) * (size_t)nc, hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_info.reserve((size_t)nc));
         hipLaunchKernelGGL(nwa::coll_info_kernel, dim3((unsigned)((nc + 255) / 256)), dim3(256), 0, st, a, a.coll, nc,
                            c->d_info.p);
-        AHIP(c, hipGetLastError());
-        AHIP(c, hipMemcpyAsync(info.data(), c->d_info.p, sizeof(nwa::CollInfo) * (size_t)nc, hipMemcpyDeviceToHost, st));
-        AHIP(c, hipStreamSynchronize(st));
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipMemcpyAsync(info.data(), c->d_info.p, sizeof(nwa::CollInfo) * (size_t)nc, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
         std::vector<int64_t> byte_off((size_t)nc + 1, 0);
         for (int64_t i = 0; i < nc; ++i) {
             if (info[(size_t)i].len < 0 || info[(size_t)i].group < 0 || info[(size_t)i].group >= ng_dev)
-                return afail(c, NW_E_STATE, "inconsistent collided read");
+                return fail(c, NW_E_STATE, "inconsistent collided read");
             byte_off[(size_t)i + 1] = byte_off[(size_t)i] + info[(size_t)i].len;
         }
         std::vector<char> bytes((size_t)std::max<int64_t>(byte_off[(size_t)nc], 1));
         for (int64_t i = 0; i < nc; ++i)
             if (info[(size_t)i].len > 0)
-                AHIP(c, hipMemcpyAsync(bytes.data() + byte_off[(size_t)i], d_reads + info[(size_t)i].start,
-                                       (size_t)info[(size_t)i].len, hipMemcpyDeviceToHost, st));
-        AHIP(c, hipStreamSynchronize(st));
+                HIP_TRY(c, hipMemcpyAsync(bytes.data() + byte_off[(size_t)i], d_reads + info[(size_t)i].start,
+                                          (size_t)info[(size_t)i].len, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
         group_collided(info, byte_off, bytes, &cgrp, &cg_count);
         cg_first.assign(cg_count.size(), -1);
         for (int64_t i = 0; i < nc; ++i)
@@ -538,11 +440,11 @@ int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offset
     c->collided = nc;
     const int64_t ng_new = (int64_t)cg_count.size(), ng = ng_dev + ng_new;
     *n_groups = ng;
-    if (ng > cap) return afail(c, NW_E_CAPACITY, "%lld groups, capacity %lld", (long long)ng, (long long)cap);
+    if (ng > cap) return fail(c, NW_E_CAPACITY, "%lld groups, capacity %lld", (long long)ng, (long long)cap);
     std::vector<uint32_t> gf((size_t)ng_dev), gc((size_t)ng_dev);
-    AHIP(c, hipMemcpy(gf.data(), a.gfirst, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost));
-    AHIP(c, hipMemcpy(gc.data(), a.gcount, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost));
-    if (group_of_read) AHIP(c, hipMemcpy(group_of_read, a.gor, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(gf.data(), a.gfirst, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(gc.data(), a.gcount, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost));
+    if (group_of_read) HIP_TRY(c, hipMemcpy(group_of_read, a.gor, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToHost));
     if (nc == 0) {
         for (int64_t g = 0; g < ng_dev; ++g) {
             first[g] = gf[(size_t)g];

@@ -25,7 +25,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -36,24 +35,20 @@
 
 #include "../../include/crispr_count.h"
 #include "../../include/crispr_nw.h"
+#include "group_device.h"
+#include "host_dev.h"
 
 namespace nwc {
 
-constexpr uint64_t kPoly = 0x9E3779B97F4A7C15ull;     // odd: a one-dword difference never cancels
-constexpr uint64_t kLenMul = 0xC2B2AE3D27D4EB4Full;
+using grp::fmix64;
+using grp::kLenMul;
+using grp::kPoly;
+using grp::wave_elect;
+
 constexpr uint32_t kNoSlot = 0xFFFFFFFFu;
 constexpr int64_t kChunkBytes = (int64_t)64 << 20;     // text per chunk by default
 constexpr int64_t kChunkReads = (int64_t)4 << 20;      // and no more reads than this
 enum { kFound = 0, kCounted = 1, kError = 2, kCollided = 3, kGroups = 4, kCounters = 8 };
-
-__host__ __device__ inline uint64_t fmix64(uint64_t h) {
-    h ^= h >> 33;
-    h *= 0xFF51AFD7ED558CCDull;
-    h ^= h >> 33;
-    h *= 0xC4CEB9FE1A85EC53ull;
-    h ^= h >> 33;
-    return h;
-}
 
 // The hash of a key from the polynomial of its zero-padded dwords (sum of dword k times
 // kPoly^(k + 1)): the length mixed in, cut to the low bits of `mask`, never 0 (0 = no key).
@@ -88,26 +83,6 @@ struct Args {
     uint32_t* coll;            // [cn] the chunk's collided reads (chunk index), any order
     uint32_t* counters;
 };
-
-// Dword k of the len bytes at byte position p of text (4k < len): bytes at or past len as
-// zero.  Aligned loads only, and only of words that hold one of the len bytes.
-__device__ inline uint32_t text_dword(const uint32_t* text, int64_t p, int k, int len) {
-    const int64_t a = p + 4 * (int64_t)k;
-    const unsigned sh = (unsigned)(a & 3);
-    const uint32_t* w = text + (a >> 2);
-    const int left = len - 4 * k;
-    const int nb = left < 4 ? left : 4;
-    uint32_t v = w[0] >> (8 * sh);
-    if (sh && nb > 4 - (int)sh) v |= w[1] << (32 - 8 * sh);
-    if (nb < 4) v &= (1u << (8 * nb)) - 1u;
-    return v;
-}
-
-__device__ inline uint64_t shfl64(uint64_t v, int src) {
-    const int lo = __shfl((int)(uint32_t)v, src, 64);
-    const int hi = __shfl((int)(uint32_t)(v >> 32), src, 64);
-    return ((uint64_t)(uint32_t)hi << 32) | (uint32_t)lo;
-}
 
 __global__ __launch_bounds__(256) void nwc_find_kernel(Args a) {
     __shared__ uint32_t spat[32];
@@ -166,7 +141,7 @@ __global__ __launch_bounds__(256) void nwc_find_kernel(Args a) {
     const int glen = st < idx ? (int)(idx - st) : 0;
     uint64_t poly = 0, pw = kPoly;
     for (int k = 0; k < a.kw; ++k) {
-        const uint32_t v = 4 * k < glen ? text_dword(a.text, s0 + st, k, glen) : 0u;
+        const uint32_t v = 4 * k < glen ? grp::load_dword((const uint8_t*)a.text + (s0 + st), k, glen) : 0u;
         a.keys[r * a.kw + k] = v;
         poly += (uint64_t)v * pw;
         pw *= kPoly;
@@ -174,30 +149,6 @@ __global__ __launch_bounds__(256) void nwc_find_kernel(Args a) {
     a.pos[r] = (int32_t)idx;
     a.klen[r] = glen;
     a.hash[r] = finish_hash(poly, glen, a.hash_mask);
-}
-
-// Among the active lanes of the wavefront, those with equal `key` elect the lowest of them:
-// *lead = that lane (the lane itself when inactive); returns the group's size in the elected
-// lane and 0 in every other.  At most 64 rounds, one per distinct key.
-__device__ inline uint32_t wave_elect(uint64_t key, bool active, int* lead) {
-    const int lane = threadIdx.x & 63;
-    bool done = !active;
-    uint32_t cnt = 0;
-    *lead = lane;
-    for (int it = 0; it < 64; ++it) {
-        const unsigned long long act = __ballot(!done);
-        if (!act) break;
-        const int l0 = __ffsll((long long)act) - 1;
-        const uint64_t k0 = shfl64(key, l0);
-        const bool mine = !done && key == k0;
-        const unsigned long long same = __ballot(mine);
-        if (mine) {
-            done = true;
-            *lead = l0;
-            if (lane == l0) cnt = (uint32_t)__popcll(same);
-        }
-    }
-    return cnt;
 }
 
 __global__ __launch_bounds__(256) void nwc_insert_kernel(Args a) {
@@ -208,18 +159,7 @@ __global__ __launch_bounds__(256) void nwc_insert_kernel(Args a) {
     const uint32_t cnt = wave_elect(h, h != 0, &lead);
     uint32_t found = kNoSlot;
     if (cnt) {
-        uint64_t s = (h * kPoly) >> a.shift;
-        for (uint64_t probe = 0; probe <= a.cap_mask; ++probe) {      // bounded by the table size
-            unsigned long long k = __hip_atomic_load(&a.tkey[s], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (k == 0) k = atomicCAS(&a.tkey[s], 0ull, (unsigned long long)h);
-            if (k == 0 || k == h) {
-                atomicMin(&a.tfirst[s], (uint32_t)(a.r0 + r));
-                atomicAdd(&a.tcount[s], cnt);
-                found = (uint32_t)s;
-                break;
-            }
-            s = (s + 1) & a.cap_mask;
-        }
+        found = (uint32_t)grp::claim_slot(a.tkey, a.tfirst, a.tcount, h, (uint32_t)(a.r0 + r), cnt, a.shift, a.cap_mask);
         if (found == kNoSlot) a.counters[kError] = 1;   // a full table: cannot happen at load <= 1/2
     }
     found = (uint32_t)__shfl((int)found, lead, 64);
@@ -233,17 +173,6 @@ __global__ __launch_bounds__(256) void nwc_publish_kernel(Args a) {
     if (s == kNoSlot || a.tfirst[s] != (uint32_t)(a.r0 + r)) return;
     a.tlen[s] = a.klen[r];
     for (int k = 0; k < a.kw; ++k) a.tkeys[(int64_t)s * a.kw + k] = a.keys[r * a.kw + k];
-}
-
-// the lanes with `flag` append `value` to list (one atomic per wavefront)
-__device__ inline void wave_append(bool flag, uint32_t value, uint32_t* list, uint32_t* counter) {
-    const int lane = threadIdx.x & 63;
-    const unsigned long long b = __ballot(flag);
-    if (!b) return;
-    uint32_t at = 0;
-    if (lane == __ffsll((long long)b) - 1) at = atomicAdd(counter, (uint32_t)__popcll(b));
-    at = (uint32_t)__shfl((int)at, __ffsll((long long)b) - 1, 64);
-    if (flag) list[at + (uint32_t)__popcll(b & ((1ull << lane) - 1ull))] = value;
 }
 
 __global__ __launch_bounds__(256) void nwc_verify_kernel(Args a) {
@@ -261,7 +190,8 @@ __global__ __launch_bounds__(256) void nwc_verify_kernel(Args a) {
             }
         }
     }
-    wave_append(diff, (uint32_t)r, a.coll, &a.counters[kCollided]);
+    const uint32_t at = grp::wave_reserve(diff, &a.counters[kCollided]);
+    if (diff) a.coll[at] = (uint32_t)r;
 }
 
 // Whitelist: tkey / tlen / tkeys hold the host's table; tcount is the count by slot.
@@ -298,7 +228,9 @@ __global__ __launch_bounds__(256) void nwc_lookup_kernel(Args a) {
 
 __global__ __launch_bounds__(256) void nwc_occupied_kernel(Args a, uint32_t* list) {
     const uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    wave_append(s <= a.cap_mask && a.tkey[s] != 0, (uint32_t)s, list, &a.counters[kGroups]);
+    const bool used = s <= a.cap_mask && a.tkey[s] != 0;
+    const uint32_t at = grp::wave_reserve(used, &a.counters[kGroups]);
+    if (used) list[at] = (uint32_t)s;
 }
 
 __global__ __launch_bounds__(256) void nwc_gather_kernel(Args a, const uint32_t* list, int64_t ng, uint32_t* gfirst,
@@ -311,24 +243,6 @@ __global__ __launch_bounds__(256) void nwc_gather_kernel(Args a, const uint32_t*
     glen[g] = a.tlen[s];
     for (int k = 0; k < a.kw; ++k) gkeys[g * a.kw + k] = a.tkeys[(int64_t)s * a.kw + k];
 }
-
-template <class T>
-struct Buf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap && p) return hipSuccess;
-        release();
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
 
 // The polynomial of a key's zero-padded dwords, as the find kernel computes it.
 uint64_t host_hash(const uint8_t* key, int len, int kw, uint64_t mask, uint32_t* dwords) {
@@ -345,45 +259,25 @@ uint64_t host_hash(const uint8_t* key, int len, int kw, uint64_t mask, uint32_t*
 
 }  // namespace nwc
 
-struct nwc_ctx {
-    int device = 0;
+struct nwc_ctx : hd::DevContext {
     int hash_bits = 64;
     int64_t chunk_reads = 0;       // 0: by bytes
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[5] = {};
-    std::string err;
     int64_t collided = 0;
     float phase_ms[6] = {0, 0, 0, 0, 0, 0};
     // the last call's groups
     std::vector<int64_t> g_first, g_count, g_koff;
     std::vector<uint8_t> g_kbytes;
-    nwc::Buf<uint32_t> d_text, d_pat, d_keys, d_slot, d_tfirst, d_tcount, d_tkeys, d_coll, d_counters, d_list,
+    hd::DevBuf<uint32_t> d_text, d_pat, d_keys, d_slot, d_tfirst, d_tcount, d_tkeys, d_coll, d_counters, d_list,
         d_gfirst, d_gcount, d_gkeys;
-    nwc::Buf<int64_t> d_off;
-    nwc::Buf<int32_t> d_pos, d_klen, d_tlen, d_glen;
-    nwc::Buf<uint64_t> d_hash;
-    nwc::Buf<unsigned long long> d_tkey;
+    hd::DevBuf<int64_t> d_off;
+    hd::DevBuf<int32_t> d_pos, d_klen, d_tlen, d_glen;
+    hd::DevBuf<uint64_t> d_hash;
+    hd::DevBuf<unsigned long long> d_tkey;
 };
 
 namespace {
 
-int cfail(nwc_ctx* c, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
-}
-
-#define CHIP(c, expr)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return cfail((c), e_ == hipErrorOutOfMemory ? NW_E_NOMEM : NW_E_HIP, "%s: %s", #expr, \
-                         hipGetErrorString(e_));                                                  \
-    } while (0)
+using hd::fail;
 
 struct Collided {
     int64_t read;          // global read index
@@ -417,55 +311,17 @@ int hand_out(const nwc_ctx* c, int64_t* first, int64_t* count, int64_t* key_offs
 extern "C" {
 
 int nwc_create(int device, nwc_ctx** out) {
-    if (!out) return NW_E_INVALID;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return NW_E_HIP;
-    nwc_ctx* c = new nwc_ctx();
-    c->device = device;
-    bool ok = hipSetDevice(device) == hipSuccess &&
-              hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; ok && i < 5; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
-    if (!ok) {
-        nwc_destroy(c);
-        return NW_E_HIP;
-    }
-    if (const char* e = std::getenv("CRISPR_NWC_HASH_BITS")) c->hash_bits = std::max(0, std::min(64, std::atoi(e)));
+    const int rc = hd::create_context(device, 5, out);
+    if (rc != NW_OK) return rc;
+    nwc_ctx* c = *out;
+    c->hash_bits = grp::env_hash_bits("CRISPR_NWC_HASH_BITS");
     if (const char* e = std::getenv("CRISPR_NWC_CHUNK"))
         c->chunk_reads = std::max<int64_t>(0, std::min<int64_t>(std::atoll(e), 0x7FFFFFFFll));
     c->g_koff.assign(1, 0);
-    *out = c;
     return NW_OK;
 }
 
-void nwc_destroy(nwc_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    c->d_text.release();
-    c->d_pat.release();
-    c->d_keys.release();
-    c->d_slot.release();
-    c->d_tfirst.release();
-    c->d_tcount.release();
-    c->d_tkeys.release();
-    c->d_coll.release();
-    c->d_counters.release();
-    c->d_list.release();
-    c->d_gfirst.release();
-    c->d_gcount.release();
-    c->d_gkeys.release();
-    c->d_off.release();
-    c->d_pos.release();
-    c->d_klen.release();
-    c->d_tlen.release();
-    c->d_glen.release();
-    c->d_hash.release();
-    c->d_tkey.release();
-    for (hipEvent_t e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+void nwc_destroy(nwc_ctx* c) { hd::destroy_context(c); }
 
 const char* nwc_last_error(const nwc_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
@@ -489,22 +345,22 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
               int64_t key_cap, int32_t* pos, int32_t* group_of_read, int64_t* n_groups, int64_t* n_key_bytes,
               int64_t* n_found, int64_t* n_counted, float* kernel_ms) {
     if (!c) return NW_E_INVALID;
-    if (n < 0 || n > 0x7FFFFFFFll) return cfail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
+    if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
     if (!n_groups || !n_key_bytes || !n_found || !n_counted || cap < 0 || key_cap < 0)
-        return cfail(c, NW_E_INVALID, "null output");
-    if (n > 0 && (!reads || !offsets)) return cfail(c, NW_E_INVALID, "null input array");
+        return fail(c, NW_E_INVALID, "null output");
+    if (n > 0 && (!reads || !offsets)) return fail(c, NW_E_INVALID, "null input array");
     if (!pattern || m < 1 || m > NWC_MAX_PATTERN)
-        return cfail(c, NW_E_UNSUPPORTED, "pattern of %d bytes: 1 to %d are supported", (int)m, NWC_MAX_PATTERN);
+        return fail(c, NW_E_UNSUPPORTED, "pattern of %d bytes: 1 to %d are supported", (int)m, NWC_MAX_PATTERN);
     if (guide_length < 0 || guide_length > NWC_MAX_GUIDE)
-        return cfail(c, NW_E_UNSUPPORTED, "guide length %d: 0 to %d are supported", (int)guide_length, NWC_MAX_GUIDE);
+        return fail(c, NW_E_UNSUPPORTED, "guide length %d: 0 to %d are supported", (int)guide_length, NWC_MAX_GUIDE);
     const bool wl = n_wl >= 0;
-    if (wl && n_wl > 0 && !wl_offsets) return cfail(c, NW_E_INVALID, "null whitelist");
+    if (wl && n_wl > 0 && !wl_offsets) return fail(c, NW_E_INVALID, "null whitelist");
     for (int64_t k = 0; wl && k < n_wl; ++k)
-        if (wl_offsets[k + 1] < wl_offsets[k]) return cfail(c, NW_E_INVALID, "whitelist offsets do not ascend");
+        if (wl_offsets[k + 1] < wl_offsets[k]) return fail(c, NW_E_INVALID, "whitelist offsets do not ascend");
     for (int64_t r = 0; r < n; ++r) {
         const int64_t len = offsets[r + 1] - offsets[r];
-        if (len < 0) return cfail(c, NW_E_INVALID, "offsets do not ascend at read %lld", (long long)r);
-        if (len > 0x7FFFFFFFll) return cfail(c, NW_E_UNSUPPORTED, "read %lld is longer than 2^31 - 1 bytes", (long long)r);
+        if (len < 0) return fail(c, NW_E_INVALID, "offsets do not ascend at read %lld", (long long)r);
+        if (len > 0x7FFFFFFFll) return fail(c, NW_E_UNSUPPORTED, "read %lld is longer than 2^31 - 1 bytes", (long long)r);
     }
     c->collided = 0;
     std::fill(c->phase_ms, c->phase_ms + 6, 0.0f);
@@ -516,11 +372,9 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
     *n_groups = *n_key_bytes = *n_found = *n_counted = 0;
 
     const int L = guide_length, kw = (L + 3) / 4;
-    const uint64_t hash_mask = c->hash_bits >= 64 ? ~0ull : (((uint64_t)1 << c->hash_bits) - 1);
 
     // the whitelist: distinct keys in order of first line; the table of those that can be a guide
     Whitelist W;
-    int log2cap = 10;
     std::vector<unsigned long long> h_tkey;
     std::vector<int32_t> h_tlen;
     std::vector<uint32_t> h_tkeys;
@@ -530,8 +384,13 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
             std::string key((const char*)wl_bytes + wl_offsets[k], (size_t)(wl_offsets[k + 1] - wl_offsets[k]));
             if (seen.emplace(key, (int64_t)W.keys.size()).second) W.keys.push_back(std::move(key));
         }
-        while (((int64_t)1 << log2cap) < 2 * (int64_t)W.keys.size()) ++log2cap;
-        const size_t slots = (size_t)1 << log2cap;
+    }
+    // (free mode: 2^31 slots at most: a slot index is 32 bits with one value reserved; above 2^30 reads
+    //  the load passes 1/2 but stays under 1, and the probe bound still holds)
+    const grp::TableGeometry tg =
+        grp::table_geometry(wl ? (int64_t)W.keys.size() : std::min<int64_t>(n, (int64_t)1 << 30), c->hash_bits);
+    const size_t slots = tg.slots;
+    if (wl) {
         h_tkey.assign(slots, 0);
         h_tlen.assign(slots, 0);
         h_tkeys.assign(slots * (size_t)std::max(kw, 1), 0);
@@ -540,20 +399,15 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
         for (size_t k = 0; k < W.keys.size(); ++k) {
             const std::string& key = W.keys[k];
             if ((int64_t)key.size() > L) continue;            // no guide is longer than L
-            const uint64_t h = nwc::host_hash((const uint8_t*)key.data(), (int)key.size(), kw, hash_mask, dw);
-            size_t s = (size_t)((h * nwc::kPoly) >> (64 - log2cap));
+            const uint64_t h = nwc::host_hash((const uint8_t*)key.data(), (int)key.size(), kw, tg.hash_mask, dw);
+            size_t s = (size_t)((h * nwc::kPoly) >> tg.shift);
             while (h_tkey[s] != 0) s = (s + 1) & (slots - 1);   // distinct keys at load <= 1/2: ends
             h_tkey[s] = h;
             h_tlen[s] = (int32_t)key.size();
             for (int j = 0; j < kw; ++j) h_tkeys[s * (size_t)kw + (size_t)j] = dw[j];
             W.slot_key[s] = (int64_t)k;
         }
-    } else {
-        // (2^31 slots at most: a slot index is 32 bits with one value reserved; above 2^30 reads the
-        //  load passes 1/2 but stays under 1, and the probe bound still holds)
-        while (log2cap < 31 && ((int64_t)1 << log2cap) < 2 * n) ++log2cap;
     }
-    const size_t slots = (size_t)1 << log2cap;
 
     std::vector<Collided> collided;
     std::vector<uint32_t> slot_of_read;      // free mode: each counted read's slot until the groups are known
@@ -563,32 +417,32 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
     nwc::Args a{};
 
     if (n > 0) {
-        CHIP(c, hipSetDevice(c->device));
+        HIP_TRY(c, hipSetDevice(c->device));
         hipStream_t st = c->stream;
-        CHIP(c, c->d_pat.reserve(32));
-        CHIP(c, c->d_counters.reserve(nwc::kCounters));
-        CHIP(c, c->d_tkey.reserve(slots));
-        CHIP(c, c->d_tfirst.reserve(slots));
-        CHIP(c, c->d_tcount.reserve(slots));
-        CHIP(c, c->d_tlen.reserve(slots));
-        CHIP(c, c->d_tkeys.reserve(slots * (size_t)std::max(kw, 1)));
+        HIP_TRY(c, c->d_pat.reserve(32));
+        HIP_TRY(c, c->d_counters.reserve(nwc::kCounters));
+        HIP_TRY(c, c->d_tkey.reserve(slots));
+        HIP_TRY(c, c->d_tfirst.reserve(slots));
+        HIP_TRY(c, c->d_tcount.reserve(slots));
+        HIP_TRY(c, c->d_tlen.reserve(slots));
+        HIP_TRY(c, c->d_tkeys.reserve(slots * (size_t)std::max(kw, 1)));
         uint32_t pat[32] = {};
         std::memcpy(pat, pattern, (size_t)m);
-        CHIP(c, hipMemcpyAsync(c->d_pat.p, pat, sizeof pat, hipMemcpyHostToDevice, st));
-        CHIP(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(uint32_t) * nwc::kCounters, st));
-        CHIP(c, hipMemsetAsync(c->d_tcount.p, 0, sizeof(uint32_t) * slots, st));
+        HIP_TRY(c, hipMemcpyAsync(c->d_pat.p, pat, sizeof pat, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(uint32_t) * nwc::kCounters, st));
+        HIP_TRY(c, hipMemsetAsync(c->d_tcount.p, 0, sizeof(uint32_t) * slots, st));
         if (wl) {
-            CHIP(c, hipMemcpyAsync(c->d_tkey.p, h_tkey.data(), sizeof(unsigned long long) * slots, hipMemcpyHostToDevice, st));
-            CHIP(c, hipMemcpyAsync(c->d_tlen.p, h_tlen.data(), sizeof(int32_t) * slots, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(c->d_tkey.p, h_tkey.data(), sizeof(unsigned long long) * slots, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemcpyAsync(c->d_tlen.p, h_tlen.data(), sizeof(int32_t) * slots, hipMemcpyHostToDevice, st));
             if (kw > 0)
-                CHIP(c, hipMemcpyAsync(c->d_tkeys.p, h_tkeys.data(), sizeof(uint32_t) * slots * (size_t)kw,
-                                       hipMemcpyHostToDevice, st));
+                HIP_TRY(c, hipMemcpyAsync(c->d_tkeys.p, h_tkeys.data(), sizeof(uint32_t) * slots * (size_t)kw,
+                                          hipMemcpyHostToDevice, st));
         } else {
-            CHIP(c, hipMemsetAsync(c->d_tkey.p, 0, sizeof(unsigned long long) * slots, st));
-            CHIP(c, hipMemsetAsync(c->d_tfirst.p, 0xFF, sizeof(uint32_t) * slots, st));
-            CHIP(c, hipMemsetAsync(c->d_tlen.p, 0, sizeof(int32_t) * slots, st));
+            HIP_TRY(c, hipMemsetAsync(c->d_tkey.p, 0, sizeof(unsigned long long) * slots, st));
+            HIP_TRY(c, hipMemsetAsync(c->d_tfirst.p, 0xFF, sizeof(uint32_t) * slots, st));
+            HIP_TRY(c, hipMemsetAsync(c->d_tlen.p, 0, sizeof(int32_t) * slots, st));
         }
-        CHIP(c, hipStreamSynchronize(st));       // (the host tables above are read by the copies)
+        HIP_TRY(c, hipStreamSynchronize(st));       // (the host tables above are read by the copies)
         a.m = m;
         a.L = L;
         a.kw = kw;
@@ -599,9 +453,9 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
         a.tcount = c->d_tcount.p;
         a.tlen = c->d_tlen.p;
         a.tkeys = c->d_tkeys.p;
-        a.cap_mask = (uint64_t)slots - 1;
-        a.shift = 64 - log2cap;
-        a.hash_mask = hash_mask;
+        a.cap_mask = tg.cap_mask;
+        a.shift = tg.shift;
+        a.hash_mask = tg.hash_mask;
         a.counters = c->d_counters.p;
         if (!wl && want_gor) slot_of_read.assign((size_t)n, nwc::kNoSlot);
 
@@ -619,23 +473,23 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
             // the chunk keeps the phase of its first byte within a word (lead), as a resident batch would
             const int64_t cn = r1 - r0, lead = offsets[r0] & 3, base = offsets[r0] - lead, nbytes = offsets[r1] - offsets[r0];
             const size_t words = (size_t)((lead + nbytes + 3) / 4);
-            CHIP(c, c->d_text.reserve(words));
-            CHIP(c, c->d_off.reserve((size_t)cn + 1));
-            CHIP(c, c->d_pos.reserve((size_t)cn));
-            CHIP(c, c->d_klen.reserve((size_t)cn));
-            CHIP(c, c->d_hash.reserve((size_t)cn));
-            CHIP(c, c->d_keys.reserve((size_t)cn * (size_t)std::max(kw, 1)));
-            CHIP(c, c->d_slot.reserve((size_t)cn));
-            CHIP(c, c->d_coll.reserve((size_t)cn));
+            HIP_TRY(c, c->d_text.reserve(words));
+            HIP_TRY(c, c->d_off.reserve((size_t)cn + 1));
+            HIP_TRY(c, c->d_pos.reserve((size_t)cn));
+            HIP_TRY(c, c->d_klen.reserve((size_t)cn));
+            HIP_TRY(c, c->d_hash.reserve((size_t)cn));
+            HIP_TRY(c, c->d_keys.reserve((size_t)cn * (size_t)std::max(kw, 1)));
+            HIP_TRY(c, c->d_slot.reserve((size_t)cn));
+            HIP_TRY(c, c->d_coll.reserve((size_t)cn));
             const auto t0 = std::chrono::steady_clock::now();
             if (nbytes > 0) {
-                CHIP(c, hipMemsetAsync(c->d_text.p, 0, 4, st));                   // (the bytes beside the batch
-                CHIP(c, hipMemsetAsync(c->d_text.p + (words - 1), 0, 4, st));     //  in its first and last word)
-                CHIP(c, hipMemcpyAsync((uint8_t*)c->d_text.p + lead, reads + offsets[r0], (size_t)nbytes,
-                                       hipMemcpyHostToDevice, st));
+                HIP_TRY(c, hipMemsetAsync(c->d_text.p, 0, 4, st));                   // (the bytes beside the batch
+                HIP_TRY(c, hipMemsetAsync(c->d_text.p + (words - 1), 0, 4, st));     //  in its first and last word)
+                HIP_TRY(c, hipMemcpyAsync((uint8_t*)c->d_text.p + lead, reads + offsets[r0], (size_t)nbytes,
+                                          hipMemcpyHostToDevice, st));
             }
-            CHIP(c, hipMemcpyAsync(c->d_off.p, offsets + r0, sizeof(int64_t) * (size_t)(cn + 1), hipMemcpyHostToDevice, st));
-            CHIP(c, hipStreamSynchronize(st));
+            HIP_TRY(c, hipMemcpyAsync(c->d_off.p, offsets + r0, sizeof(int64_t) * (size_t)(cn + 1), hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipStreamSynchronize(st));
             c->phase_ms[5] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
             a.text = c->d_text.p;
             a.off = c->d_off.p;
@@ -648,44 +502,44 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
             a.keys = c->d_keys.p;
             a.slot = c->d_slot.p;
             a.coll = c->d_coll.p;
-            CHIP(c, hipMemsetAsync(&a.counters[nwc::kCollided], 0, sizeof(uint32_t), st));
+            HIP_TRY(c, hipMemsetAsync(&a.counters[nwc::kCollided], 0, sizeof(uint32_t), st));
             const unsigned find_grid = (unsigned)((cn + 255) / 256), lane_grid = find_grid;
-            CHIP(c, hipEventRecord(c->ev[0], st));
+            HIP_TRY(c, hipEventRecord(c->ev[0], st));
             hipLaunchKernelGGL(nwc::nwc_find_kernel, dim3(find_grid), dim3(256), 0, st, a);
-            CHIP(c, hipGetLastError());
-            CHIP(c, hipEventRecord(c->ev[1], st));
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipEventRecord(c->ev[1], st));
             if (wl) {
-                CHIP(c, hipEventRecord(c->ev[2], st));
-                CHIP(c, hipEventRecord(c->ev[3], st));
+                HIP_TRY(c, hipEventRecord(c->ev[2], st));
+                HIP_TRY(c, hipEventRecord(c->ev[3], st));
                 hipLaunchKernelGGL(nwc::nwc_lookup_kernel, dim3(lane_grid), dim3(256), 0, st, a);
-                CHIP(c, hipGetLastError());
+                HIP_TRY(c, hipGetLastError());
             } else {
                 hipLaunchKernelGGL(nwc::nwc_insert_kernel, dim3(lane_grid), dim3(256), 0, st, a);
-                CHIP(c, hipGetLastError());
-                CHIP(c, hipEventRecord(c->ev[2], st));
+                HIP_TRY(c, hipGetLastError());
+                HIP_TRY(c, hipEventRecord(c->ev[2], st));
                 hipLaunchKernelGGL(nwc::nwc_publish_kernel, dim3(lane_grid), dim3(256), 0, st, a);
-                CHIP(c, hipGetLastError());
-                CHIP(c, hipEventRecord(c->ev[3], st));
+                HIP_TRY(c, hipGetLastError());
+                HIP_TRY(c, hipEventRecord(c->ev[3], st));
                 hipLaunchKernelGGL(nwc::nwc_verify_kernel, dim3(lane_grid), dim3(256), 0, st, a);
-                CHIP(c, hipGetLastError());
+                HIP_TRY(c, hipGetLastError());
             }
-            CHIP(c, hipEventRecord(c->ev[4], st));
-            CHIP(c, hipMemcpyAsync(ctr, a.counters, sizeof ctr, hipMemcpyDeviceToHost, st));
-            if (pos) CHIP(c, hipMemcpyAsync(pos + r0, a.pos, sizeof(int32_t) * (size_t)cn, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipEventRecord(c->ev[4], st));
+            HIP_TRY(c, hipMemcpyAsync(ctr, a.counters, sizeof ctr, hipMemcpyDeviceToHost, st));
+            if (pos) HIP_TRY(c, hipMemcpyAsync(pos + r0, a.pos, sizeof(int32_t) * (size_t)cn, hipMemcpyDeviceToHost, st));
             if (want_gor) {
                 h_slot.resize((size_t)cn);
-                CHIP(c, hipMemcpyAsync(h_slot.data(), a.slot, sizeof(uint32_t) * (size_t)cn, hipMemcpyDeviceToHost, st));
+                HIP_TRY(c, hipMemcpyAsync(h_slot.data(), a.slot, sizeof(uint32_t) * (size_t)cn, hipMemcpyDeviceToHost, st));
             }
-            CHIP(c, hipStreamSynchronize(st));
+            HIP_TRY(c, hipStreamSynchronize(st));
             for (int i = 0; i < 4; ++i) {
                 float ms = 0.0f;
-                CHIP(c, hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
+                HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[i], c->ev[i + 1]));
                 c->phase_ms[i] += ms;
                 kms += ms;
             }
             if (ctr[nwc::kError])
-                return cfail(c, NW_E_STATE, "the hash table's probe bound was reached (%zu slots, %lld reads)", slots,
-                             (long long)n);
+                return fail(c, NW_E_STATE, "the hash table's probe bound was reached (%zu slots, %lld reads)", slots,
+                            (long long)n);
             if (want_gor) {
                 if (wl)
                     for (int64_t i = 0; i < cn; ++i)
@@ -694,21 +548,21 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
                     std::copy(h_slot.begin(), h_slot.end(), slot_of_read.begin() + r0);
             }
             const int64_t nc = ctr[nwc::kCollided];
-            if (nc > cn) return cfail(c, NW_E_STATE, "inconsistent collided count");
+            if (nc > cn) return fail(c, NW_E_STATE, "inconsistent collided count");
             if (nc > 0) {      // equal hashes, different guides: their keys come back, the host groups them
                 h_coll.resize((size_t)nc);
                 h_klen.resize((size_t)cn);
                 h_keys.resize((size_t)cn * (size_t)std::max(kw, 1));
                 h_slot.resize((size_t)cn);
-                CHIP(c, hipMemcpy(h_coll.data(), a.coll, sizeof(uint32_t) * (size_t)nc, hipMemcpyDeviceToHost));
-                CHIP(c, hipMemcpy(h_klen.data(), a.klen, sizeof(int32_t) * (size_t)cn, hipMemcpyDeviceToHost));
-                CHIP(c, hipMemcpy(h_slot.data(), a.slot, sizeof(uint32_t) * (size_t)cn, hipMemcpyDeviceToHost));
+                HIP_TRY(c, hipMemcpy(h_coll.data(), a.coll, sizeof(uint32_t) * (size_t)nc, hipMemcpyDeviceToHost));
+                HIP_TRY(c, hipMemcpy(h_klen.data(), a.klen, sizeof(int32_t) * (size_t)cn, hipMemcpyDeviceToHost));
+                HIP_TRY(c, hipMemcpy(h_slot.data(), a.slot, sizeof(uint32_t) * (size_t)cn, hipMemcpyDeviceToHost));
                 if (kw > 0)
-                    CHIP(c, hipMemcpy(h_keys.data(), a.keys, sizeof(uint32_t) * (size_t)cn * (size_t)kw, hipMemcpyDeviceToHost));
+                    HIP_TRY(c, hipMemcpy(h_keys.data(), a.keys, sizeof(uint32_t) * (size_t)cn * (size_t)kw, hipMemcpyDeviceToHost));
                 std::sort(h_coll.begin(), h_coll.end());
                 for (uint32_t i : h_coll) {
                     if (i >= (uint32_t)cn || h_klen[i] < 0 || h_klen[i] > L || h_slot[i] == nwc::kNoSlot)
-                        return cfail(c, NW_E_STATE, "inconsistent collided read");
+                        return fail(c, NW_E_STATE, "inconsistent collided read");
                     collided.push_back({r0 + (int64_t)i, h_slot[i],
                                         std::string((const char*)(h_keys.data() + (size_t)i * (size_t)kw), (size_t)h_klen[i])});
                 }
@@ -723,7 +577,7 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
         std::vector<uint32_t> tcount;
         if (n > 0) {
             tcount.resize(slots);
-            CHIP(c, hipMemcpy(tcount.data(), a.tcount, sizeof(uint32_t) * slots, hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(tcount.data(), a.tcount, sizeof(uint32_t) * slots, hipMemcpyDeviceToHost));
         }
         const size_t ng = W.keys.size();
         c->g_first.assign(ng, -1);
@@ -737,36 +591,36 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
         *n_counted = ctr[nwc::kCounted];
     } else if (n > 0) {
         hipStream_t st = c->stream;
-        CHIP(c, c->d_list.reserve((size_t)std::min<int64_t>((int64_t)slots, n)));
-        CHIP(c, hipEventRecord(c->ev[0], st));
+        HIP_TRY(c, c->d_list.reserve((size_t)std::min<int64_t>((int64_t)slots, n)));
+        HIP_TRY(c, hipEventRecord(c->ev[0], st));
         hipLaunchKernelGGL(nwc::nwc_occupied_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, st, a, c->d_list.p);
-        CHIP(c, hipGetLastError());
+        HIP_TRY(c, hipGetLastError());
         uint32_t ngd = 0;
-        CHIP(c, hipMemcpyAsync(&ngd, &a.counters[nwc::kGroups], sizeof ngd, hipMemcpyDeviceToHost, st));
-        CHIP(c, hipStreamSynchronize(st));
+        HIP_TRY(c, hipMemcpyAsync(&ngd, &a.counters[nwc::kGroups], sizeof ngd, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
         const int64_t ng_dev = ngd;
-        if (ng_dev > n) return cfail(c, NW_E_STATE, "inconsistent group count");
+        if (ng_dev > n) return fail(c, NW_E_STATE, "inconsistent group count");
         std::vector<uint32_t> gslot((size_t)ng_dev), gfirst((size_t)ng_dev), gcount((size_t)ng_dev), gkeys;
         std::vector<int32_t> glen((size_t)ng_dev);
         if (ng_dev > 0) {
-            CHIP(c, c->d_gfirst.reserve((size_t)ng_dev));
-            CHIP(c, c->d_gcount.reserve((size_t)ng_dev));
-            CHIP(c, c->d_glen.reserve((size_t)ng_dev));
-            CHIP(c, c->d_gkeys.reserve((size_t)ng_dev * (size_t)std::max(kw, 1)));
+            HIP_TRY(c, c->d_gfirst.reserve((size_t)ng_dev));
+            HIP_TRY(c, c->d_gcount.reserve((size_t)ng_dev));
+            HIP_TRY(c, c->d_glen.reserve((size_t)ng_dev));
+            HIP_TRY(c, c->d_gkeys.reserve((size_t)ng_dev * (size_t)std::max(kw, 1)));
             hipLaunchKernelGGL(nwc::nwc_gather_kernel, dim3((unsigned)((ng_dev + 255) / 256)), dim3(256), 0, st, a,
                                c->d_list.p, ng_dev, c->d_gfirst.p, c->d_gcount.p, c->d_glen.p, c->d_gkeys.p);
-            CHIP(c, hipGetLastError());
-            CHIP(c, hipEventRecord(c->ev[1], st));
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipEventRecord(c->ev[1], st));
             gkeys.resize((size_t)ng_dev * (size_t)std::max(kw, 1));
-            CHIP(c, hipMemcpyAsync(gslot.data(), c->d_list.p, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost, st));
-            CHIP(c, hipMemcpyAsync(gfirst.data(), c->d_gfirst.p, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost, st));
-            CHIP(c, hipMemcpyAsync(gcount.data(), c->d_gcount.p, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost, st));
-            CHIP(c, hipMemcpyAsync(glen.data(), c->d_glen.p, sizeof(int32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(gslot.data(), c->d_list.p, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(gfirst.data(), c->d_gfirst.p, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(gcount.data(), c->d_gcount.p, sizeof(uint32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(glen.data(), c->d_glen.p, sizeof(int32_t) * (size_t)ng_dev, hipMemcpyDeviceToHost, st));
             if (kw > 0)
-                CHIP(c, hipMemcpyAsync(gkeys.data(), c->d_gkeys.p, sizeof(uint32_t) * (size_t)ng_dev * (size_t)kw,
-                                       hipMemcpyDeviceToHost, st));
-            CHIP(c, hipStreamSynchronize(st));
-            CHIP(c, hipEventElapsedTime(&c->phase_ms[4], c->ev[0], c->ev[1]));
+                HIP_TRY(c, hipMemcpyAsync(gkeys.data(), c->d_gkeys.p, sizeof(uint32_t) * (size_t)ng_dev * (size_t)kw,
+                                          hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipStreamSynchronize(st));
+            HIP_TRY(c, hipEventElapsedTime(&c->phase_ms[4], c->ev[0], c->ev[1]));
             kms += c->phase_ms[4];
         }
         // the slots in order of first appearance (the firsts are distinct read indices)
@@ -776,8 +630,8 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
         std::vector<int32_t> rank_of_slot(slots, -1);            // slot -> rank among the device groups
         for (int64_t i = 0; i < ng_dev; ++i) {
             const size_t g = (size_t)order[(size_t)i];
-            if (glen[g] < 0 || glen[g] > L || (int64_t)gfirst[g] >= n) return cfail(c, NW_E_STATE, "inconsistent group");
-            if (gslot[g] >= slots) return cfail(c, NW_E_STATE, "inconsistent group");
+            if (glen[g] < 0 || glen[g] > L || (int64_t)gfirst[g] >= n) return fail(c, NW_E_STATE, "inconsistent group");
+            if (gslot[g] >= slots) return fail(c, NW_E_STATE, "inconsistent group");
             rank_of_slot[gslot[g]] = (int32_t)i;
         }
         // the collided reads leave their slot's count and form groups of their own
@@ -786,7 +640,7 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
         std::vector<const std::string*> cg_key;
         for (size_t i = 0; i < collided.size(); ++i) {
             const int32_t rk = collided[i].slot < slots ? rank_of_slot[collided[i].slot] : -1;
-            if (rk < 0) return cfail(c, NW_E_STATE, "collided read of an empty slot");
+            if (rk < 0) return fail(c, NW_E_STATE, "collided read of an empty slot");
             --gcount[(size_t)order[(size_t)rk]];
             auto ins = cseen.emplace(collided[i].key, (int64_t)cg_first.size());
             if (ins.second) {
@@ -820,7 +674,7 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
             c->g_koff.push_back((int64_t)c->g_kbytes.size());
         }
         *n_counted = counted;
-        if (counted != (int64_t)ctr[nwc::kFound]) return cfail(c, NW_E_STATE, "the counts do not add up to the found reads");
+        if (counted != (int64_t)ctr[nwc::kFound]) return fail(c, NW_E_STATE, "the counts do not add up to the found reads");
         if (want_gor) {
             for (int64_t r = 0; r < n; ++r) {
                 const uint32_t s = slot_of_read[(size_t)r];
@@ -829,7 +683,7 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
                     continue;
                 }
                 const int32_t rk = s < slots ? rank_of_slot[s] : -1;
-                if (rk < 0) return cfail(c, NW_E_STATE, "read %lld in an empty slot", (long long)r);
+                if (rk < 0) return fail(c, NW_E_STATE, "read %lld in an empty slot", (long long)r);
                 group_of_read[r] = (int32_t)dev_id[(size_t)rk];
             }
             for (size_t k = 0; k < collided.size(); ++k)
@@ -841,9 +695,9 @@ int nwc_count(nwc_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t 
     *n_key_bytes = (int64_t)c->g_kbytes.size();
     const int rc = hand_out(c, first, count, key_offsets, key_bytes, cap, key_cap);
     if (rc == NW_E_CAPACITY)
-        return cfail(c, rc, "%lld groups with %lld key bytes, capacity %lld and %lld", (long long)*n_groups,
-                     (long long)*n_key_bytes, (long long)cap, (long long)key_cap);
-    if (rc != NW_OK) return cfail(c, rc, "null group array");
+        return fail(c, rc, "%lld groups with %lld key bytes, capacity %lld and %lld", (long long)*n_groups,
+                    (long long)*n_key_bytes, (long long)cap, (long long)key_cap);
+    if (rc != NW_OK) return fail(c, rc, "null group array");
     return NW_OK;
 }
 

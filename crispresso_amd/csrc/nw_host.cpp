@@ -12,7 +12,6 @@
 #include <chrono>
 #include <cctype>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -21,6 +20,7 @@
 
 #include "../../include/crispr_nw.h"
 #include "front_device.h"
+#include "host_dev.h"
 #include "host_pool.h"
 #include "nw_device.h"
 #include "nw_edna.h"
@@ -31,25 +31,8 @@ constexpr int kMaxRef = 8192;       // the exact multi-wave kernel (nw_exact.hip
 constexpr int kMaxRefWave = 1024;   // the band, stream and one-wave kernels
 constexpr int kMaxLds = 160 * 1024;
 
-template <class T>
-struct DevBuf {
-    T* p = nullptr;
-    size_t cap = 0;  // elements
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    DevBuf() = default;
-    DevBuf(const DevBuf&) = delete;
-    ~DevBuf() {   // (with its context: nw_destroy)
-        if (p) (void)hipFree(p);
-    }
-};
+using hd::DevBuf;
+using hd::fail;
 
 }  // namespace
 
@@ -365,30 +348,12 @@ void tmark(nw_ctx* c, const ChunkPlan& p, hipStream_t cs, const char* what) {
     (void)hipEventRecord(slot.second, cs);
 }
 
-int fail(nw_ctx* c, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
-}
-
 // a look-back launch's epoch: new per launch, never 0 (30 bits, nw_common.h lookback_excl)
 unsigned next_epoch(nw_ctx* c) {
     c->epoch = (c->epoch + 1) & 0x3fffffffu;
     if (c->epoch == 0) c->epoch = 1;
     return c->epoch;
 }
-
-#define HIP_OR_FAIL(ctx, expr)                                                        \
-    do {                                                                              \
-        hipError_t e_ = (expr);                                                       \
-        if (e_ != hipSuccess)                                                         \
-            return fail(ctx, e_ == hipErrorOutOfMemory ? NW_E_NOMEM : NW_E_HIP,       \
-                        "%s failed: %s", #expr, hipGetErrorString(e_));               \
-    } while (0)
 
 // One amplicon's score tables (host side): the int8 profile of the exact kernel and
 // the markup bits of the band walk (codes each row scores > 0 against).
@@ -537,14 +502,14 @@ int upload_shared(nw_ctx* c) {
         for (int code = 0; code < 16; ++code)
             sub16[(size_t)ca * 4 + code / 4] |= (uint32_t)(uint8_t)(int8_t)(nw::kEdna[ca][code] * c->scale)
                                                 << (8 * (code % 4));
-    HIP_OR_FAIL(c, c->d_sub16.reserve(sub16.size()));
-    HIP_OR_FAIL(c, hipMemcpy(c->d_sub16.p, sub16.data(), sub16.size() * 4, hipMemcpyHostToDevice));
-    HIP_OR_FAIL(c, c->d_lut6.reserve(256));
-    HIP_OR_FAIL(c, c->d_lut.reserve(256));
-    HIP_OR_FAIL(c, c->d_btab.reserve(btab.size()));
-    HIP_OR_FAIL(c, hipMemcpy(c->d_lut6.p, lut6.data(), 256, hipMemcpyHostToDevice));
-    HIP_OR_FAIL(c, hipMemcpy(c->d_lut.p, lut.data(), 256, hipMemcpyHostToDevice));
-    HIP_OR_FAIL(c, hipMemcpy(c->d_btab.p, btab.data(), btab.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, c->d_sub16.reserve(sub16.size()));
+    HIP_TRY(c, hipMemcpy(c->d_sub16.p, sub16.data(), sub16.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(c, c->d_lut6.reserve(256));
+    HIP_TRY(c, c->d_lut.reserve(256));
+    HIP_TRY(c, c->d_btab.reserve(btab.size()));
+    HIP_TRY(c, hipMemcpy(c->d_lut6.p, lut6.data(), 256, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_lut.p, lut.data(), 256, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->d_btab.p, btab.data(), btab.size() * 4, hipMemcpyHostToDevice));
     c->shared_key = key;
     return NW_OK;
 }
@@ -588,9 +553,9 @@ int upload_profiles(nw_ctx* c, const std::vector<std::string>& refs, std::vector
         std::memcpy(host.data() + o.spos, t.seed_pos.data(), t.seed_pos.size() * 2);
         std::memcpy(host.data() + o.cls, t.cls.data(), t.cls.size() * 4);
     }
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));   // no kernel may still read the old arena
-    HIP_OR_FAIL(c, c->d_arena.reserve(host.size()));
-    HIP_OR_FAIL(c, hipMemcpy(c->d_arena.p, host.data(), host.size(), hipMemcpyHostToDevice));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));   // no kernel may still read the old arena
+    HIP_TRY(c, c->d_arena.reserve(host.size()));
+    HIP_TRY(c, hipMemcpy(c->d_arena.p, host.data(), host.size(), hipMemcpyHostToDevice));
     profs->resize(refs.size());
     for (size_t g = 0; g < refs.size(); ++g) {
         const Off& o = offs[g];
@@ -653,12 +618,12 @@ int configure_long(nw_ctx* c, Scratch& S, int64_t n, AmpConfig& ac) {
     int64_t grid = std::max<int64_t>(1, std::min<int64_t>((int64_t)c->num_cus * per_cu, std::max<int64_t>(n, 1)));
     if (!ac.exact_tb_lds) {
         grid = std::max<int64_t>(1, std::min<int64_t>(grid, (2ll << 30) / ac.exact_slab));
-        HIP_OR_FAIL(c, S.d_tb.reserve((size_t)(ac.exact_slab * grid)));
+        HIP_TRY(c, S.d_tb.reserve((size_t)(ac.exact_slab * grid)));
     }
     ac.exact_grid = (int)grid;
     ac.exact_full = true;
-    HIP_OR_FAIL(c, S.d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
-    HIP_OR_FAIL(c, S.d_fallback_count.reserve(nw::kChunkCounters));
+    HIP_TRY(c, S.d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
+    HIP_TRY(c, S.d_fallback_count.reserve(nw::kChunkCounters));
     return NW_OK;
 }
 
@@ -696,7 +661,7 @@ int configure_wave(nw_ctx* c, const Switches& sw, Scratch& S, int64_t n, AmpConf
     cfg.grid = c->num_cus * per_cu;
     if (cfg.tb_mode == nw::TB_GLOBAL_FULL) {
         const int64_t per_wave = nw::tb_bytes_per_wave(R, c->lb_max);
-        HIP_OR_FAIL(c, S.d_tb.reserve((size_t)per_wave * cfg.grid * cfg.wpb));
+        HIP_TRY(c, S.d_tb.reserve((size_t)per_wave * cfg.grid * cfg.wpb));
     }
     ac.cfg = cfg;
     // exact multi-wave kernel for the work lists (the reads no band certifies)
@@ -707,7 +672,7 @@ int configure_wave(nw_ctx* c, const Switches& sw, Scratch& S, int64_t n, AmpConf
         int grid = c->num_cus;
         if (!ac.exact_tb_lds) {
             grid = (int)std::max<int64_t>(1, std::min<int64_t>(grid, (1ll << 30) / std::max<int64_t>(ac.exact_slab, 1)));
-            HIP_OR_FAIL(c, S.d_tb.reserve((size_t)(ac.exact_slab * grid)));
+            HIP_TRY(c, S.d_tb.reserve((size_t)(ac.exact_slab * grid)));
         }
         if (sw.exact_multi_grid > 0) grid = std::min(grid, sw.exact_multi_grid);   // split the list between the kernels
         if (ac.exact_lds > 0 && ac.exact_lds <= kMaxLds) ac.exact_grid = grid;
@@ -715,8 +680,8 @@ int configure_wave(nw_ctx* c, const Switches& sw, Scratch& S, int64_t n, AmpConf
     // -endweight: the band certificate assumes free end gaps; every read goes through
     // the exact kernel (nw_align_kernel), which takes both
     if (c->end_weight) {
-        HIP_OR_FAIL(c, S.d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
-        HIP_OR_FAIL(c, S.d_fallback_count.reserve(nw::kChunkCounters));
+        HIP_TRY(c, S.d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
+        HIP_TRY(c, S.d_fallback_count.reserve(nw::kChunkCounters));
         return NW_OK;
     }
     // certified diagonal band (default): scores and biases within int16, amplicon
@@ -777,7 +742,7 @@ int configure_wave(nw_ctx* c, const Switches& sw, Scratch& S, int64_t n, AmpConf
                 ac.wide_words = nw::band_region_words(La, c->lb_max, nw::kWideDiags);
                 ac.wide_lb_cap = La + nw::kWideDiags - 1;
                 rbytes = std::max(rbytes, ac.wide_pairs * ac.wide_stride);
-                HIP_OR_FAIL(c, S.d_fallback2.reserve((size_t)std::max<int64_t>(n, 1)));
+                HIP_TRY(c, S.d_fallback2.reserve((size_t)std::max<int64_t>(n, 1)));
             } else {
                 ac.wide_fill.grid = 0;
             }
@@ -793,34 +758,34 @@ int configure_wave(nw_ctx* c, const Switches& sw, Scratch& S, int64_t n, AmpConf
                                                                                  (int64_t)c->num_cus * occ_fill));
                     ac.wf_walk.grid = (int)std::max<int64_t>(1, std::min<int64_t>((2 * ac.wf_pairs + wide_walk_wpb - 1) / wide_walk_wpb,
                                                                                  (int64_t)c->num_cus * occ_walk));
-                    HIP_OR_FAIL(c, S.d_wf_region.reserve((size_t)(ac.wf_pairs * ac.wide_stride)));
-                    HIP_OR_FAIL(c, S.d_wf_list.reserve((size_t)std::max<int64_t>(n, 1)));
+                    HIP_TRY(c, S.d_wf_region.reserve((size_t)(ac.wf_pairs * ac.wide_stride)));
+                    HIP_TRY(c, S.d_wf_list.reserve((size_t)std::max<int64_t>(n, 1)));
                 }
             }
-            HIP_OR_FAIL(c, S.d_bregion.reserve((size_t)rbytes));
-            HIP_OR_FAIL(c, S.d_order.reserve((size_t)std::max<int64_t>(n, 1)));
-            HIP_OR_FAIL(c, S.d_redo.reserve((size_t)std::max<int64_t>(n, 1)));
-            HIP_OR_FAIL(c, S.d_redo_flags.reserve((size_t)std::max<int64_t>(n, 1)));
-            HIP_OR_FAIL(c, S.d_lb.reserve((size_t)nw::band_lookback_words(n)));
-            HIP_OR_FAIL(c, S.d_sort_key.reserve((size_t)std::max<int64_t>(n, 1)));
+            HIP_TRY(c, S.d_bregion.reserve((size_t)rbytes));
+            HIP_TRY(c, S.d_order.reserve((size_t)std::max<int64_t>(n, 1)));
+            HIP_TRY(c, S.d_redo.reserve((size_t)std::max<int64_t>(n, 1)));
+            HIP_TRY(c, S.d_redo_flags.reserve((size_t)std::max<int64_t>(n, 1)));
+            HIP_TRY(c, S.d_lb.reserve((size_t)nw::band_lookback_words(n)));
+            HIP_TRY(c, S.d_sort_key.reserve((size_t)std::max<int64_t>(n, 1)));
             // 64 entries per classify wavefront: 4 per block of 256 reads, ceil(n / 256) + 1 blocks
-            HIP_OR_FAIL(c, S.d_cert_q.reserve((size_t)std::max<int64_t>(n, 1) + 1024));
-            HIP_OR_FAIL(c, S.d_cert_cnt.reserve((size_t)std::max<int64_t>(n, 1) / 64 + 16));
+            HIP_TRY(c, S.d_cert_q.reserve((size_t)std::max<int64_t>(n, 1) + 1024));
+            HIP_TRY(c, S.d_cert_cnt.reserve((size_t)std::max<int64_t>(n, 1) / 64 + 16));
             if (c->call.seed_on) {
-                HIP_OR_FAIL(c, S.d_seed.reserve((size_t)std::max<int64_t>(n, 1)));
-                HIP_OR_FAIL(c, S.d_seed2.reserve((size_t)std::max<int64_t>(n, 1)));
+                HIP_TRY(c, S.d_seed.reserve((size_t)std::max<int64_t>(n, 1)));
+                HIP_TRY(c, S.d_seed2.reserve((size_t)std::max<int64_t>(n, 1)));
                 // the segment sort pads each 4096-read segment's seeded list to an even length (one
                 // entry per segment at most): the list, its flags and its compaction hold n + n/4096 + 2
                 const size_t nseed = (size_t)(n + n / 4096 + 2);
-                HIP_OR_FAIL(c, S.d_seed_list.reserve(nseed));
-                HIP_OR_FAIL(c, S.d_seed_flags.reserve(nseed));
-                HIP_OR_FAIL(c, S.d_seed_list2.reserve(nseed));
+                HIP_TRY(c, S.d_seed_list.reserve(nseed));
+                HIP_TRY(c, S.d_seed_flags.reserve(nseed));
+                HIP_TRY(c, S.d_seed_list2.reserve(nseed));
             }
             ac.use_diag = true;
         }
     }
-    HIP_OR_FAIL(c, S.d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
-    HIP_OR_FAIL(c, S.d_fallback_count.reserve(nw::kChunkCounters));
+    HIP_TRY(c, S.d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
+    HIP_TRY(c, S.d_fallback_count.reserve(nw::kChunkCounters));
     return NW_OK;
 }
 
@@ -980,17 +945,17 @@ int nw_batch_upload(nw_ctx* c, const char* reads, const int64_t* offsets, int64_
     c->n = n;
     c->lb_max = lb_max;
     c->cells = cells;
-    HIP_OR_FAIL(c, c->d_reads.reserve((size_t)nbytes + 512));   // the walk DMAs whole 256-B chunks
-    HIP_OR_FAIL(c, c->d_offsets.reserve((size_t)n + 1));
+    HIP_TRY(c, c->d_reads.reserve((size_t)nbytes + 512));   // the walk DMAs whole 256-B chunks
+    HIP_TRY(c, c->d_offsets.reserve((size_t)n + 1));
     if (c->out_mode == NW_OUT_ROWS)
-        HIP_OR_FAIL(c, c->d_out.reserve((size_t)std::max<int64_t>(n, 1) * 3 * stride_for(La, lb_max)));
-    HIP_OR_FAIL(c, c->d_stats.reserve((size_t)std::max<int64_t>(n, 1)));
+        HIP_TRY(c, c->d_out.reserve((size_t)std::max<int64_t>(n, 1) * 3 * stride_for(La, lb_max)));
+    HIP_TRY(c, c->d_stats.reserve((size_t)std::max<int64_t>(n, 1)));
     c->resident_ok = false;
     c->bytes_full = true;
     c->batch_pk = nw::KernelArgs{};
-    if (nbytes) HIP_OR_FAIL(c, hipMemcpyAsync(c->d_reads.p, reads + base, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
-    HIP_OR_FAIL(c, hipMemcpyAsync(c->d_offsets.p, rel.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, c->stream));
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    if (nbytes) HIP_TRY(c, hipMemcpyAsync(c->d_reads.p, reads + base, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_offsets.p, rel.data(), sizeof(int64_t) * (size_t)(n + 1), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->reads_bias = 0;
     const Switches sw = read_switches();
     int rc = configure(c, sw, c->sc[0], n);
@@ -1041,28 +1006,28 @@ int nw_front::set_packed_batch(nw_ctx* c, const PackedSrc& src, const int64_t* o
     c->n = n;
     c->lb_max = lb_max;
     c->cells = cells;
-    HIP_OR_FAIL(c, c->d_reads.reserve((size_t)nbytes + 512 + 16));
-    HIP_OR_FAIL(c, c->d_offsets.reserve((size_t)n + 1));
-    HIP_OR_FAIL(c, c->d_stats.reserve((size_t)n));
-    HIP_OR_FAIL(c, c->d_packed.reserve((size_t)(pk_hi - P0) + 64));
-    HIP_OR_FAIL(c, c->d_exc_pos.reserve((size_t)std::max<int64_t>(n_exc, 1)));
-    HIP_OR_FAIL(c, c->d_exc_byte.reserve((size_t)std::max<int64_t>(n_exc, 1)));
-    HIP_OR_FAIL(c, c->d_lens.reserve((size_t)(8 * ngroups + 2 * n + 64)));
+    HIP_TRY(c, c->d_reads.reserve((size_t)nbytes + 512 + 16));
+    HIP_TRY(c, c->d_offsets.reserve((size_t)n + 1));
+    HIP_TRY(c, c->d_stats.reserve((size_t)n));
+    HIP_TRY(c, c->d_packed.reserve((size_t)(pk_hi - P0) + 64));
+    HIP_TRY(c, c->d_exc_pos.reserve((size_t)std::max<int64_t>(n_exc, 1)));
+    HIP_TRY(c, c->d_exc_byte.reserve((size_t)std::max<int64_t>(n_exc, 1)));
+    HIP_TRY(c, c->d_lens.reserve((size_t)(8 * ngroups + 2 * n + 64)));
     std::vector<int64_t> gb((size_t)ngroups);
     for (int64_t g = 0; g < ngroups; ++g) gb[(size_t)g] = offsets[g * nw::kLenGroup];
     c->resident_ok = false;
-    if (src.ready) HIP_OR_FAIL(c, hipStreamWaitEvent(c->stream, src.ready, 0));
-    HIP_OR_FAIL(c, hipMemcpyAsync(c->d_packed.p + (q0 - P0), packed + q0, (size_t)(pk_hi - q0), kind, c->stream));
+    if (src.ready) HIP_TRY(c, hipStreamWaitEvent(c->stream, src.ready, 0));
+    HIP_TRY(c, hipMemcpyAsync(c->d_packed.p + (q0 - P0), packed + q0, (size_t)(pk_hi - q0), kind, c->stream));
     if (n_exc) {
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_exc_pos.p, exc_pos, 8 * (size_t)n_exc, kind, c->stream));
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_exc_byte.p, exc_byte, (size_t)n_exc, kind, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_exc_pos.p, exc_pos, 8 * (size_t)n_exc, kind, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_exc_byte.p, exc_byte, (size_t)n_exc, kind, c->stream));
     }
     if (src.on_device)
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p, src.gbase, 8 * (size_t)ngroups, kind, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_lens.p, src.gbase, 8 * (size_t)ngroups, kind, c->stream));
     else
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p, gb.data(), 8 * (size_t)ngroups, kind, c->stream));
-    HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p + 8 * ngroups, src.lens, 2 * (size_t)n, kind, c->stream));
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_lens.p, gb.data(), 8 * (size_t)ngroups, kind, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_lens.p + 8 * ngroups, src.lens, 2 * (size_t)n, kind, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     c->reads_bias = base0 & ~(int64_t)15;
     const Switches sw = read_switches();
     int rc = configure(c, sw, c->sc[0], n);
@@ -1087,9 +1052,9 @@ int nw_front::set_packed_batch(nw_ctx* c, const PackedSrc& src, const int64_t* o
         c->batch_pk.pk_call_lo = 0;
         c->bytes_full = false;
     } else {   // the exact kernels read bytes: unpack once
-        HIP_OR_FAIL(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, P0, base0, offsets[n], c->d_exc_pos.p,
-                                         c->d_exc_byte.p, 0, n_exc, c->d_reads.p, c->reads_bias, c->stream, &ls));
-        HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, P0, base0, offsets[n], c->d_exc_pos.p,
+                                     c->d_exc_byte.p, 0, n_exc, c->d_reads.p, c->reads_bias, c->stream, &ls));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->bytes_full = true;
     }
     c->ran = false;
@@ -1173,8 +1138,8 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
         // the band path writes every read's run count and zeroes its counters in its
         // first kernel (nw_band_classify): no memset launches in the chunk's chain
         if (!c->ac.use_diag || p.n <= 0) {
-            HIP_OR_FAIL(c, hipMemsetAsync(p.s->d_nops.p, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(p.n, 1), cs));
-            HIP_OR_FAIL(c, hipMemsetAsync(p.s->d_opsctl.p, 0, nw::kSpillCtl * sizeof(int32_t), cs));
+            HIP_TRY(c, hipMemsetAsync(p.s->d_nops.p, 0, sizeof(int32_t) * (size_t)std::max<int64_t>(p.n, 1), cs));
+            HIP_TRY(c, hipMemsetAsync(p.s->d_opsctl.p, 0, nw::kSpillCtl * sizeof(int32_t), cs));
         }
     }
     if (c->ac.use_diag) {
@@ -1238,10 +1203,10 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
                 a.wf_taken_n = p.s->d_fallback_count.p + nw::kCntWfTaken;
             }
         }
-        HIP_OR_FAIL(c, nw::launch_band_sort(a, next_epoch(c), cs));
+        HIP_TRY(c, nw::launch_band_sort(a, next_epoch(c), cs));
         tmark(c, p, cs, "classify+sort");
         const bool pev = p.phase_events;   // (resident passes that ask for them)
-        if (pev) HIP_OR_FAIL(c, hipEventRecord(c->ev_sort, cs));
+        if (pev) HIP_TRY(c, hipEventRecord(c->ev_sort, cs));
         const int64_t pairs = (p.n + 2) / 2;   // (the second level's list may hold one hole)
         // level 1 (16 diagonals) over the sorted reads; what it cannot certify -> redo list
         // -> level 2 (32 diagonals) -> the exact int32 kernel.  Kernels clamp the pair
@@ -1285,17 +1250,17 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
             af.band_pair_hi = c->ac.wf_pairs;
             af.fallback_list = p.s->d_fallback2.p + base;
             af.fallback_count = p.s->d_fallback_count.p + nw::kCntWideGiveUp;
-            HIP_OR_FAIL(c, hipEventRecord(c->ev_wf0, cs));
-            HIP_OR_FAIL(c, hipStreamWaitEvent(wf_side, c->ev_wf0, 0));
-            HIP_OR_FAIL(c, nw::launch_band(nw::kWideDiags, af, c->ac.wf_fill, c->ac.wf_walk, wf_side, nullptr));
-            HIP_OR_FAIL(c, hipEventRecord(c->ev_wf1, wf_side));
+            HIP_TRY(c, hipEventRecord(c->ev_wf0, cs));
+            HIP_TRY(c, hipStreamWaitEvent(wf_side, c->ev_wf0, 0));
+            HIP_TRY(c, nw::launch_band(nw::kWideDiags, af, c->ac.wf_fill, c->ac.wf_walk, wf_side, nullptr));
+            HIP_TRY(c, hipEventRecord(c->ev_wf1, wf_side));
         }
         for (int lvl = two ? 0 : 1; lvl < 2; ++lvl) {
             nw::KernelArgs al = a;
             al.redo_direct = lvl == 1 ? direct : 0;
             const int W = lvl == 0 ? 16 : 32;
             if (lvl == 1 && two) {
-                HIP_OR_FAIL(c, nw::launch_redo_compact(a, p.n, next_epoch(c), cs));
+                HIP_TRY(c, nw::launch_redo_compact(a, p.n, next_epoch(c), cs));
                 tmark(c, p, cs, "redo");
                 al.band_order = p.s->d_redo.p;
                 al.band_count = a.redo_count;
@@ -1314,13 +1279,13 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
                 nw::KernelArgs ap = al;
                 ap.band_pair_lo = lo;
                 ap.band_pair_hi = std::min(pairs, lo + pp);
-                HIP_OR_FAIL(c, nw::launch_band(W, ap, fc, wc, cs, pev && first && lo == 0 ? c->ev_fill : nullptr));
+                HIP_TRY(c, nw::launch_band(W, ap, fc, wc, cs, pev && first && lo == 0 ? c->ev_fill : nullptr));
                 tmark(c, p, cs, W == 16 ? "fill16+walk16" : "fill32+walk32");
-                if (pev && first && lo == 0) HIP_OR_FAIL(c, hipEventRecord(c->ev_walk, cs));
+                if (pev && first && lo == 0) HIP_TRY(c, hipEventRecord(c->ev_walk, cs));
             }
             if (first && p.split_to) {   // the latency-bound rest of the chunk on the tail stream
-                HIP_OR_FAIL(c, hipEventRecord(p.split_ev, cs));
-                HIP_OR_FAIL(c, hipStreamWaitEvent(p.split_to, p.split_ev, 0));
+                HIP_TRY(c, hipEventRecord(p.split_ev, cs));
+                HIP_TRY(c, hipStreamWaitEvent(p.split_to, p.split_ev, 0));
                 cs = p.split_to;
             }
         }
@@ -1336,12 +1301,12 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
             ac.wf_list = nullptr;
             ac.redo_list = p.s->d_seed_list2.p;
             ac.redo_count = p.s->d_fallback_count.p + nw::kCntSeededL2;
-            HIP_OR_FAIL(c, nw::launch_redo_compact(ac, p.n + p.n / 4096 + 2, next_epoch(c), cs, true));
+            HIP_TRY(c, nw::launch_redo_compact(ac, p.n + p.n / 4096 + 2, next_epoch(c), cs, true));
             tmark(c, p, cs, "seed compact");
             a.seed_list = ac.redo_list;
             a.seed_count = ac.redo_count;
         }
-        if (pev) HIP_OR_FAIL(c, hipEventRecord(c->ev_l2, cs));
+        if (pev) HIP_TRY(c, hipEventRecord(c->ev_l2, cs));
         a.work_list = a.fallback_list;   // what the 16 / 32 levels could not certify
         a.work_count = p.s->d_fallback_count.p + nw::kCntExact;
         a.redo_direct = direct;
@@ -1361,7 +1326,7 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
             aw.band_pair_hi = c->ac.wide_pairs;
             aw.fallback_list = p.s->d_fallback2.p + base;
             aw.fallback_count = p.s->d_fallback_count.p + nw::kCntWideGiveUp;
-            HIP_OR_FAIL(c, nw::launch_band(nw::kWideDiags, aw, c->ac.wide_fill, c->ac.wide_walk, cs, nullptr));
+            HIP_TRY(c, nw::launch_band(nw::kWideDiags, aw, c->ac.wide_fill, c->ac.wide_walk, cs, nullptr));
             tmark(c, p, cs, "wide");
             a.work_list = aw.fallback_list;
             a.work_count = aw.fallback_count;
@@ -1370,19 +1335,19 @@ int launch_range(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* out) 
         // the wide-first launch's give-ups are on the exact kernel's list: the join (nothing between the
         // first level and here reads what that launch writes -- its reads are on no other list, its region
         // is its own, the lists it shares with the wide launch above grow by atomics)
-        if (L.wf_chunk) HIP_OR_FAIL(c, hipStreamWaitEvent(cs, c->ev_wf1, 0));
-        HIP_OR_FAIL(c, launch_work(c, a, p.exact_small, cs));
+        if (L.wf_chunk) HIP_TRY(c, hipStreamWaitEvent(cs, c->ev_wf1, 0));
+        HIP_TRY(c, launch_work(c, a, p.exact_small, cs));
         tmark(c, p, cs, "exact");
         return NW_OK;
     }
-    HIP_OR_FAIL(c, hipMemsetAsync(p.s->d_fallback_count.p, 0, nw::kChunkCounters * sizeof(int32_t), cs));
+    HIP_TRY(c, hipMemsetAsync(p.s->d_fallback_count.p, 0, nw::kChunkCounters * sizeof(int32_t), cs));
     if (c->ac.exact_full) {   // long amplicon: every read through the multi-wave kernel
         if (p.n > 0)
-            HIP_OR_FAIL(c, nw::launch_exact(a, c->ac.exact_grid, c->ac.exact_lds, c->ac.exact_tb_lds, c->ac.exact_slab, false,
-                                            cs));
+            HIP_TRY(c, nw::launch_exact(a, c->ac.exact_grid, c->ac.exact_lds, c->ac.exact_tb_lds, c->ac.exact_slab, false,
+                                        cs));
         return NW_OK;
     }
-    if (p.n > 0) HIP_OR_FAIL(c, launch_work(c, a, p.exact_small, cs));   // every read (null work list)
+    if (p.n > 0) HIP_TRY(c, launch_work(c, a, p.exact_small, cs));   // every read (null work list)
     return NW_OK;
 }
 
@@ -1396,14 +1361,14 @@ int ops_reserve(nw_ctx* c, const Switches& sw, Scratch& S, int64_t chunk, int64_
     c->spill_cap = sw.spill_words;
     c->staging_cap = chunk * c->ops_slot + c->spill_cap;
     c->ops_stride = chunk;
-    HIP_OR_FAIL(c, S.d_slots.reserve((size_t)(2 * chunk * c->ops_slot)));   // column-major + row-major areas
-    HIP_OR_FAIL(c, S.d_nops.reserve((size_t)chunk));
-    HIP_OR_FAIL(c, S.d_spill.reserve((size_t)c->spill_cap));
-    HIP_OR_FAIL(c, S.d_opsctl.reserve(nw::kSpillCtl));
-    HIP_OR_FAIL(c, c->d_ctl64.reserve(2 * nw::kOpsCtlAll));   // a dual call: one block per pass
-    HIP_OR_FAIL(c, S.d_lb.reserve((size_t)nw::band_lookback_words(chunk)));
-    HIP_OR_FAIL(c, c->d_opsoff.reserve((size_t)std::max<int64_t>(n, 1) + 1));
-    HIP_OR_FAIL(c, S.d_staging.reserve((size_t)c->staging_cap));
+    HIP_TRY(c, S.d_slots.reserve((size_t)(2 * chunk * c->ops_slot)));   // column-major + row-major areas
+    HIP_TRY(c, S.d_nops.reserve((size_t)chunk));
+    HIP_TRY(c, S.d_spill.reserve((size_t)c->spill_cap));
+    HIP_TRY(c, S.d_opsctl.reserve(nw::kSpillCtl));
+    HIP_TRY(c, c->d_ctl64.reserve(2 * nw::kOpsCtlAll));   // a dual call: one block per pass
+    HIP_TRY(c, S.d_lb.reserve((size_t)nw::band_lookback_words(chunk)));
+    HIP_TRY(c, c->d_opsoff.reserve((size_t)std::max<int64_t>(n, 1) + 1));
+    HIP_TRY(c, S.d_staging.reserve((size_t)c->staging_cap));
     return NW_OK;
 }
 
@@ -1420,8 +1385,8 @@ int launch_range_ops(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* o
     // only the compaction writes the set's staging array: it waits for the copy of the
     // runs it held two chunks ago, and (the running base of ctl) for the previous
     // chunk's compaction on the other stream; the kernels before it wait for neither
-    if (staging_free) HIP_OR_FAIL(c, hipStreamWaitEvent(cs, staging_free, 0));
-    if (prev_done) HIP_OR_FAIL(c, hipStreamWaitEvent(cs, prev_done, 0));
+    if (staging_free) HIP_TRY(c, hipStreamWaitEvent(cs, staging_free, 0));
+    if (prev_done) HIP_TRY(c, hipStreamWaitEvent(cs, prev_done, 0));
     nw::OpsCounts cnt{};
     cnt.fallback = p.s->d_fallback_count.p;
     cnt.prio = c->tail_prio;
@@ -1444,14 +1409,14 @@ int launch_range_ops(nw_ctx* c, const ChunkPlan& p, int64_t base, ChunkLaunch* o
     nw::OpsKnown kn{};
     if (p.known) {   // the known alignment (computed on the upload stream) before any copy takes it
         const KnownSet& K = *p.known;
-        HIP_OR_FAIL(c, hipStreamWaitEvent(cs, K.ev_known, 0));
+        HIP_TRY(c, hipStreamWaitEvent(cs, K.ev_known, 0));
         kn = nw::OpsKnown{K.d_kstat.p, K.d_kmisc.p, K.d_kslots.p, K.d_kslots.p + 2 * nw::kOpsSlot, nw::kOpsSlot};
     }
-    HIP_OR_FAIL(c, nw::launch_ops_compact(p.s->d_nops.p, p.s->d_slots.p, c->ops_slot, c->ops_stride, p.s->d_spill.p, p.n,
-                                          p.s->d_lb.p, next_epoch(c), parity, c->d_ctl64.p + p.ctl_pass * nw::kOpsCtlAll,
-                                          c->d_opsoff.p + p.out_off + base,
-                                          p.s->d_staging.p, c->staging_cap, p.s->d_opsctl.p, cnt, cs, hctl, host,
-                                          c->d_stats.p + p.out_off + base, p.known ? &kn : nullptr));
+    HIP_TRY(c, nw::launch_ops_compact(p.s->d_nops.p, p.s->d_slots.p, c->ops_slot, c->ops_stride, p.s->d_spill.p, p.n,
+                                      p.s->d_lb.p, next_epoch(c), parity, c->d_ctl64.p + p.ctl_pass * nw::kOpsCtlAll,
+                                      c->d_opsoff.p + p.out_off + base,
+                                      p.s->d_staging.p, c->staging_cap, p.s->d_opsctl.p, cnt, cs, hctl, host,
+                                      c->d_stats.p + p.out_off + base, p.known ? &kn : nullptr));
     tmark(c, p, cs, "compact");
     return NW_OK;
 }
@@ -1486,17 +1451,17 @@ int ops_events(nw_ctx* c, size_t chunks) {
         }
         return hipSuccess;
     };
-    HIP_OR_FAIL(c, grow(c->ev_in, hipEventDisableTiming));
-    HIP_OR_FAIL(c, grow(c->ev_cs, hipEventDefault));
-    HIP_OR_FAIL(c, grow(c->ev_ce, hipEventDefault));
-    HIP_OR_FAIL(c, grow(c->ev_out, hipEventDisableTiming));
-    HIP_OR_FAIL(c, grow(c->ev_bulk, hipEventDisableTiming));
-    HIP_OR_FAIL(c, grow(c->ev_up, hipEventDisableTiming));
+    HIP_TRY(c, grow(c->ev_in, hipEventDisableTiming));
+    HIP_TRY(c, grow(c->ev_cs, hipEventDefault));
+    HIP_TRY(c, grow(c->ev_ce, hipEventDefault));
+    HIP_TRY(c, grow(c->ev_out, hipEventDisableTiming));
+    HIP_TRY(c, grow(c->ev_bulk, hipEventDisableTiming));
+    HIP_TRY(c, grow(c->ev_up, hipEventDisableTiming));
     if ((int64_t)chunks > c->h_ctl_chunks) {
         if (c->h_ctl) (void)hipHostFree(c->h_ctl);
         c->h_ctl = nullptr;
         c->h_ctl_chunks = 0;
-        HIP_OR_FAIL(c, hipHostMalloc((void**)&c->h_ctl, sizeof(int64_t) * nw::kOpsCtl * chunks, hipHostMallocDefault));
+        HIP_TRY(c, hipHostMalloc((void**)&c->h_ctl, sizeof(int64_t) * nw::kOpsCtl * chunks, hipHostMallocDefault));
         c->h_ctl_chunks = (int64_t)chunks;
     }
     return NW_OK;
@@ -1525,7 +1490,7 @@ int nw_batch_run_async(nw_ctx* c) {
     if (!c) return NW_E_INVALID;
     if (c->ref.empty() || !c->d_offsets.p) return fail(c, NW_E_STATE, "no batch uploaded");
     (void)hipSetDevice(c->device);
-    HIP_OR_FAIL(c, hipEventRecord(c->ev0, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));
     int rc;
     c->call_done = false;
     c->phases_recorded = c->phase_events;
@@ -1544,14 +1509,14 @@ int nw_batch_run_async(nw_ctx* c) {
         if (c->ac.use_diag && c->n > 0) {
             p.zero_ctl = c->d_ctl64.p;
         } else {
-            HIP_OR_FAIL(c, hipMemsetAsync(c->d_ctl64.p, 0, nw::kOpsCtlAll * sizeof(int64_t), c->stream));
+            HIP_TRY(c, hipMemsetAsync(c->d_ctl64.p, 0, nw::kOpsCtlAll * sizeof(int64_t), c->stream));
         }
         rc = launch_range_ops(c, p, 0, &c->last_launch);
     } else {
         rc = launch_range(c, p, 0, &c->last_launch);
     }
     if (rc) return rc;
-    HIP_OR_FAIL(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     c->ran = true;
     return NW_OK;
 }
@@ -1559,10 +1524,10 @@ int nw_batch_run_async(nw_ctx* c) {
 int nw_batch_sync(nw_ctx* c, float* kernel_ms) {
     if (!c) return NW_E_INVALID;
     (void)hipSetDevice(c->device);
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (kernel_ms) {
         *kernel_ms = 0.0f;
-        if (c->ran) HIP_OR_FAIL(c, hipEventElapsedTime(kernel_ms, c->ev0, c->ev1));
+        if (c->ran) HIP_TRY(c, hipEventElapsedTime(kernel_ms, c->ev0, c->ev1));
     }
     return NW_OK;
 }
@@ -1571,23 +1536,23 @@ int nw_batch_download(nw_ctx* c, char* aln_out, int64_t stride, nw_stat* stats) 
     if (!c) return NW_E_INVALID;
     if (!c->ran) return fail(c, NW_E_STATE, "nothing has run");
     (void)hipSetDevice(c->device);
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (c->n == 0) return NW_OK;
     if (aln_out && c->out_mode == NW_OUT_OPS) return fail(c, NW_E_STATE, "ops output: use nw_batch_download_ops");
     if (c->ac.use_diag) {   // the band path's single-pass scans report a cut-off look-back here
         int32_t fb[nw::kCntLookback + 1] = {};
-        HIP_OR_FAIL(c, hipMemcpy(fb, c->sc[0].d_fallback_count.p, sizeof fb, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(fb, c->sc[0].d_fallback_count.p, sizeof fb, hipMemcpyDeviceToHost));
         if (fb[nw::kCntLookback]) return ops_error(c, nw::kOpsErrLookback);
     }
     if (stats)
-        HIP_OR_FAIL(c, hipMemcpy(stats, c->d_stats.p, sizeof(nw::Stat) * (size_t)c->n, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(stats, c->d_stats.p, sizeof(nw::Stat) * (size_t)c->n, hipMemcpyDeviceToHost));
     if (aln_out) {
         if (stride < c->ac.stride) return fail(c, NW_E_INVALID, "stride %lld < required %lld", (long long)stride, (long long)c->ac.stride);
         if (stride == c->ac.stride) {
-            HIP_OR_FAIL(c, hipMemcpy(aln_out, c->d_out.p, (size_t)c->n * 3 * c->ac.stride, hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(aln_out, c->d_out.p, (size_t)c->n * 3 * c->ac.stride, hipMemcpyDeviceToHost));
         } else {
-            HIP_OR_FAIL(c, hipMemcpy2D(aln_out, (size_t)stride, c->d_out.p, (size_t)c->ac.stride, (size_t)c->ac.stride,
-                                       (size_t)c->n * 3, hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy2D(aln_out, (size_t)stride, c->d_out.p, (size_t)c->ac.stride, (size_t)c->ac.stride,
+                                   (size_t)c->n * 3, hipMemcpyDeviceToHost));
         }
     }
     return NW_OK;
@@ -1609,14 +1574,14 @@ int nw_batch_kernel_times(nw_ctx* c, float* fill_ms, float* walk_ms, float* rest
     if (!c) return NW_E_INVALID;
     if (!c->ran) return fail(c, NW_E_STATE, "nothing has run");
     (void)hipSetDevice(c->device);
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     float total = 0.0f, f = 0.0f, w = 0.0f;
-    HIP_OR_FAIL(c, hipEventElapsedTime(&total, c->ev0, c->ev1));
+    HIP_TRY(c, hipEventElapsedTime(&total, c->ev0, c->ev1));
     if (c->ac.use_diag && c->n > 0 && !c->phases_recorded)
         return fail(c, NW_E_STATE, "the last run recorded no phase events (nw_batch_set_phase_events)");
     if (c->ac.use_diag && c->n > 0) {
-        HIP_OR_FAIL(c, hipEventElapsedTime(&f, c->ev0, c->ev_fill));
-        HIP_OR_FAIL(c, hipEventElapsedTime(&w, c->ev_fill, c->ev_walk));
+        HIP_TRY(c, hipEventElapsedTime(&f, c->ev0, c->ev_fill));
+        HIP_TRY(c, hipEventElapsedTime(&w, c->ev_fill, c->ev_walk));
     } else {
         f = total;
     }
@@ -1630,7 +1595,7 @@ int nw_batch_device_output(nw_ctx* c, void** d_aln, int64_t* stride, void** d_st
     if (!c) return NW_E_INVALID;
     if (!c->ran || c->n <= 0) return fail(c, NW_E_STATE, "no resident batch (run nw_batch_run_async first)");
     (void)hipSetDevice(c->device);
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     if (d_aln) *d_aln = c->d_out.p;
     if (stride) *stride = c->ac.stride;
     if (d_stats) *d_stats = c->d_stats.p;
@@ -1643,16 +1608,16 @@ int nw_batch_device_ops(nw_ctx* c, void** d_ops, void** d_ops_off, void** d_stat
     if (!c->ran || c->n <= 0 || c->out_mode != NW_OUT_OPS)
         return fail(c, NW_E_STATE, "no resident ops-mode batch (nw_batch_set_output(NW_OUT_OPS), run first)");
     (void)hipSetDevice(c->device);
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     int64_t ctl[nw::kOpsCtl];
-    HIP_OR_FAIL(c, hipMemcpy(ctl, c->d_ctl64.p, sizeof ctl, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(ctl, c->d_ctl64.p, sizeof ctl, hipMemcpyDeviceToHost));
     int rc = ops_error(c, ctl[nw::kCtlError]);
     if (rc) return rc;
     if (!c->bytes_full) {   // a packed batch: classify wrote the DP reads' bytes only; now every read's
-        HIP_OR_FAIL(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, c->batch_pos0 / 4, c->batch_base0,
-                                         c->batch_base0 + c->batch_nbytes, c->d_exc_pos.p, c->d_exc_byte.p, 0,
-                                         c->batch_n_exc, c->d_reads.p, c->reads_bias, c->stream));
-        HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, c->batch_pos0 / 4, c->batch_base0,
+                                     c->batch_base0 + c->batch_nbytes, c->d_exc_pos.p, c->d_exc_byte.p, 0,
+                                     c->batch_n_exc, c->d_reads.p, c->reads_bias, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
         c->bytes_full = true;
     }
     if (d_ops) *d_ops = c->sc[0].d_staging.p;   // one chunk: the call's runs from offset 0
@@ -1747,15 +1712,15 @@ int nw_align_multi(nw_ctx* c, const char* refs, const int64_t* ref_offsets, int3
         std::memcpy(sreads.data() + soff[(size_t)s], reads + offsets[r], (size_t)(offsets[r + 1] - offsets[r]));
     }
     c->resident_ok = false;
-    HIP_OR_FAIL(c, c->d_reads.reserve(sreads.size() + 512));
-    HIP_OR_FAIL(c, c->d_offsets.reserve((size_t)n + 1));
-    HIP_OR_FAIL(c, c->d_out.reserve((size_t)std::max<int64_t>(n, 1) * 3 * stride_all));
-    HIP_OR_FAIL(c, c->d_stats.reserve((size_t)std::max<int64_t>(n, 1)));
-    HIP_OR_FAIL(c, c->sc[0].d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
-    HIP_OR_FAIL(c, c->sc[0].d_fallback2.reserve((size_t)std::max<int64_t>(n, 1)));   // indexed like d_fallback (+ group base)
+    HIP_TRY(c, c->d_reads.reserve(sreads.size() + 512));
+    HIP_TRY(c, c->d_offsets.reserve((size_t)n + 1));
+    HIP_TRY(c, c->d_out.reserve((size_t)std::max<int64_t>(n, 1) * 3 * stride_all));
+    HIP_TRY(c, c->d_stats.reserve((size_t)std::max<int64_t>(n, 1)));
+    HIP_TRY(c, c->sc[0].d_fallback.reserve((size_t)std::max<int64_t>(n, 1)));
+    HIP_TRY(c, c->sc[0].d_fallback2.reserve((size_t)std::max<int64_t>(n, 1)));   // indexed like d_fallback (+ group base)
     if (!sreads.empty())
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_reads.p, sreads.data(), sreads.size(), hipMemcpyHostToDevice, c->stream));
-    HIP_OR_FAIL(c, hipMemcpyAsync(c->d_offsets.p, soff.data(), sizeof(int64_t) * soff.size(), hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_reads.p, sreads.data(), sreads.size(), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_offsets.p, soff.data(), sizeof(int64_t) * soff.size(), hipMemcpyHostToDevice, c->stream));
     // every amplicon's tables uploaded once (one arena); then one kernel group per amplicon,
     // queued back to back on the stream (configure() may grow buffers between groups)
     std::vector<std::string> amps((size_t)n_refs);
@@ -1788,10 +1753,10 @@ int nw_align_multi(nw_ctx* c, const char* refs, const int64_t* ref_offsets, int3
         c->ac.stride = stride_all;   // every group's rows in one array
         if ((rc = launch_range(c, p, lo, &c->last_launch))) return rc;
     }
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     // back to the callers' order
     std::vector<nw::Stat> st((size_t)n);
-    if (n) HIP_OR_FAIL(c, hipMemcpy(st.data(), c->d_stats.p, sizeof(nw::Stat) * (size_t)n, hipMemcpyDeviceToHost));
+    if (n) HIP_TRY(c, hipMemcpy(st.data(), c->d_stats.p, sizeof(nw::Stat) * (size_t)n, hipMemcpyDeviceToHost));
     if (stats)
         for (int64_t s = 0; s < n; ++s) std::memcpy(&stats[order[(size_t)s]], &st[(size_t)s], sizeof(nw::Stat));
     if (aln_out) {
@@ -1800,7 +1765,7 @@ int nw_align_multi(nw_ctx* c, const char* refs, const int64_t* ref_offsets, int3
             const int64_t lo = first[(size_t)g], hi = first[(size_t)g + 1];
             if (hi == lo) continue;
             rows.resize((size_t)(hi - lo) * 3 * stride_all);
-            HIP_OR_FAIL(c, hipMemcpy(rows.data(), c->d_out.p + lo * 3 * stride_all, rows.size(), hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy(rows.data(), c->d_out.p + lo * 3 * stride_all, rows.size(), hipMemcpyDeviceToHost));
             for (int64_t s = lo; s < hi; ++s)
                 for (int k = 0; k < 3; ++k)
                     std::memcpy(aln_out + (order[(size_t)s] * 3 + k) * stride, rows.data() + ((s - lo) * 3 + k) * stride_all,
@@ -1836,20 +1801,20 @@ int nw_batch_download_ops(nw_ctx* c, uint32_t* ops_out, int64_t ops_cap, int64_t
     if (!c) return NW_E_INVALID;
     if (!c->ran || c->out_mode != NW_OUT_OPS) return fail(c, NW_E_STATE, "no ops-mode run (nw_batch_set_output)");
     (void)hipSetDevice(c->device);
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     int64_t ctl[nw::kOpsCtl];
-    HIP_OR_FAIL(c, hipMemcpy(ctl, c->d_ctl64.p, sizeof ctl, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(ctl, c->d_ctl64.p, sizeof ctl, hipMemcpyDeviceToHost));
     int rc = ops_error(c, ctl[nw::kCtlError]);
     if (rc) return rc;
     if (c->n > 0) {
-        if (stats) HIP_OR_FAIL(c, hipMemcpy(stats, c->d_stats.p, sizeof(nw::Stat) * (size_t)c->n, hipMemcpyDeviceToHost));
-        if (ops_off) HIP_OR_FAIL(c, hipMemcpy(ops_off, c->d_opsoff.p, sizeof(int64_t) * (size_t)c->n, hipMemcpyDeviceToHost));
+        if (stats) HIP_TRY(c, hipMemcpy(stats, c->d_stats.p, sizeof(nw::Stat) * (size_t)c->n, hipMemcpyDeviceToHost));
+        if (ops_off) HIP_TRY(c, hipMemcpy(ops_off, c->d_opsoff.p, sizeof(int64_t) * (size_t)c->n, hipMemcpyDeviceToHost));
     }
     if (ops_off) ops_off[c->n] = ctl[nw::kCtlChunkTotal];
     if (ctl[nw::kCtlChunkTotal] > ops_cap)
         return fail(c, NW_E_CAPACITY, "ops_cap %lld < %lld runs", (long long)ops_cap, (long long)ctl[nw::kCtlChunkTotal]);
     if (ctl[nw::kCtlChunkTotal] > 0 && ops_out)
-        HIP_OR_FAIL(c, hipMemcpy(ops_out, c->sc[0].d_staging.p, sizeof(uint32_t) * (size_t)ctl[nw::kCtlChunkTotal], hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(ops_out, c->sc[0].d_staging.p, sizeof(uint32_t) * (size_t)ctl[nw::kCtlChunkTotal], hipMemcpyDeviceToHost));
     return NW_OK;
 }
 
@@ -1935,20 +1900,20 @@ int known_prepare(nw_ctx* c, const std::string& A, hipStream_t ks, int set = 0) 
     std::vector<uint32_t> w2((size_t)(La + 15) / 16 + 2, 0u);
     for (int p = 0; p < La; ++p) w2[(size_t)p / 16] |= (uint32_t)(((unsigned char)A[p] >> 1) & 3u) << (2 * (p % 16));
     const int64_t tbw = c->ac.cfg.tb_mode == nw::TB_GLOBAL_FULL ? nw::tb_bytes_per_wave(c->ac.cfg.R, c->lb_max) : 0;
-    HIP_OR_FAIL(c, K.d_kbytes.reserve((size_t)La + 64));
-    HIP_OR_FAIL(c, K.d_koff.reserve(2));
-    HIP_OR_FAIL(c, K.d_k2.reserve(w2.size()));
-    HIP_OR_FAIL(c, K.d_kslots.reserve(2 * nw::kOpsSlot + 4096));   // column-major + row-major slot, spill
-    HIP_OR_FAIL(c, K.d_kstat.reserve(1));
-    HIP_OR_FAIL(c, K.d_kmisc.reserve(16));
-    HIP_OR_FAIL(c, K.d_kfb.reserve(1));
-    HIP_OR_FAIL(c, K.d_ktb.reserve((size_t)std::max<int64_t>(tbw * c->ac.cfg.wpb, 16)));
-    if (!K.ev_known) HIP_OR_FAIL(c, hipEventCreateWithFlags(&K.ev_known, hipEventDisableTiming));
+    HIP_TRY(c, K.d_kbytes.reserve((size_t)La + 64));
+    HIP_TRY(c, K.d_koff.reserve(2));
+    HIP_TRY(c, K.d_k2.reserve(w2.size()));
+    HIP_TRY(c, K.d_kslots.reserve(2 * nw::kOpsSlot + 4096));   // column-major + row-major slot, spill
+    HIP_TRY(c, K.d_kstat.reserve(1));
+    HIP_TRY(c, K.d_kmisc.reserve(16));
+    HIP_TRY(c, K.d_kfb.reserve(1));
+    HIP_TRY(c, K.d_ktb.reserve((size_t)std::max<int64_t>(tbw * c->ac.cfg.wpb, 16)));
+    if (!K.ev_known) HIP_TRY(c, hipEventCreateWithFlags(&K.ev_known, hipEventDisableTiming));
     const int64_t off[2] = {0, La};
-    HIP_OR_FAIL(c, hipMemcpyAsync(K.d_kbytes.p, A.data(), (size_t)La, hipMemcpyHostToDevice, ks));
-    HIP_OR_FAIL(c, hipMemcpyAsync(K.d_koff.p, off, sizeof off, hipMemcpyHostToDevice, ks));
-    HIP_OR_FAIL(c, hipMemcpyAsync(K.d_k2.p, w2.data(), 4 * w2.size(), hipMemcpyHostToDevice, ks));
-    HIP_OR_FAIL(c, hipMemsetAsync(K.d_kmisc.p, 0, 16 * sizeof(int32_t), ks));
+    HIP_TRY(c, hipMemcpyAsync(K.d_kbytes.p, A.data(), (size_t)La, hipMemcpyHostToDevice, ks));
+    HIP_TRY(c, hipMemcpyAsync(K.d_koff.p, off, sizeof off, hipMemcpyHostToDevice, ks));
+    HIP_TRY(c, hipMemcpyAsync(K.d_k2.p, w2.data(), 4 * w2.size(), hipMemcpyHostToDevice, ks));
+    HIP_TRY(c, hipMemsetAsync(K.d_kmisc.p, 0, 16 * sizeof(int32_t), ks));
     nw::KernelArgs ka{};
     ka.reads = K.d_kbytes.p;
     ka.offsets = K.d_koff.p;
@@ -1974,8 +1939,8 @@ int known_prepare(nw_ctx* c, const std::string& A, hipStream_t ks, int set = 0) 
     ka.ops_ctl = K.d_kmisc.p + 1;
     nw::LaunchCfg one = c->ac.cfg;
     one.grid = 1;
-    HIP_OR_FAIL(c, nw::launch(ka, one, ks));
-    HIP_OR_FAIL(c, hipEventRecord(K.ev_known, ks));
+    HIP_TRY(c, nw::launch(ka, one, ks));
+    HIP_TRY(c, hipEventRecord(K.ev_known, ks));
     K.on = true;
     return NW_OK;
 }
@@ -2078,7 +2043,7 @@ struct OpsCall {
     int64_t in_pass(int64_t k) const { return dual ? k >> 1 : k; }
 };
 
-// Every exit of ops_call, the HIP_OR_FAIL ones too, leaves no per-call state behind.
+// Every exit of ops_call, the HIP_TRY ones too, leaves no per-call state behind.
 struct CallReset {
     nw_ctx* c;
     ~CallReset() {
@@ -2099,11 +2064,11 @@ int queue_uploads(nw_ctx* c, OpsCall& o) {
     const PackedInput* pk = o.pk;
     const int64_t* offsets = o.offsets;
     const int64_t n = o.n;
-    HIP_OR_FAIL(c, hipEventRecord(c->ev_h0, c->s_in));
+    HIP_TRY(c, hipEventRecord(c->ev_h0, c->s_in));
     if (pk && o.upload && pk->n_exc > 0) {
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_exc_pos.p, pk->exc_pos, sizeof(int64_t) * (size_t)pk->n_exc,
-                                      hipMemcpyHostToDevice, c->s_in));
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_exc_byte.p, pk->exc_byte, (size_t)pk->n_exc, hipMemcpyHostToDevice, c->s_in));
+        HIP_TRY(c, hipMemcpyAsync(c->d_exc_pos.p, pk->exc_pos, sizeof(int64_t) * (size_t)pk->n_exc,
+                                  hipMemcpyHostToDevice, c->s_in));
+        HIP_TRY(c, hipMemcpyAsync(c->d_exc_byte.p, pk->exc_byte, (size_t)pk->n_exc, hipMemcpyHostToDevice, c->s_in));
         o.h2d_bytes += 9 * pk->n_exc;
     }
     // Packed input with the reads' lengths (nw_align_ops_packed_lens): per read its uint16
@@ -2122,7 +2087,7 @@ int queue_uploads(nw_ctx* c, OpsCall& o) {
             if (c->h_lens) (void)hipHostFree(c->h_lens);
             c->h_lens = nullptr;
             c->h_lens_cap = 0;
-            HIP_OR_FAIL(c, hipHostMalloc((void**)&c->h_lens, (size_t)need, hipHostMallocDefault));
+            HIP_TRY(c, hipHostMalloc((void**)&c->h_lens, (size_t)need, hipHostMallocDefault));
             c->h_lens_cap = need;
         }
         if (c->d_lens.reserve((size_t)(8 * ngroups_len + 2 * n + 64)) != hipSuccess)
@@ -2130,7 +2095,7 @@ int queue_uploads(nw_ctx* c, OpsCall& o) {
         int64_t* gb = (int64_t*)c->h_lens;
         for (int64_t g = 0; g < ngroups_len; ++g) gb[g] = offsets[g * nw::kLenGroup];
         std::memcpy(c->h_lens + 8 * ngroups_len, pk->lens + o.chunks[0].lo, 2 * (size_t)n0);
-        HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p, c->h_lens, (size_t)need, hipMemcpyHostToDevice, c->s_in));
+        HIP_TRY(c, hipMemcpyAsync(c->d_lens.p, c->h_lens, (size_t)need, hipMemcpyHostToDevice, c->s_in));
         o.h2d_bytes += need;
     }
     for (int64_t k = 0; o.upload && k < o.nchunks; ++k) {
@@ -2141,31 +2106,31 @@ int queue_uploads(nw_ctx* c, OpsCall& o) {
         // ahead of chunk 1's bases: fewer copies, fewer gaps on the engine (C4 16.9 -> 16.4 ms,
         // C5 17.2 -> 17.0 ms against one lengths copy per chunk)
         if (o.lens_on && k == (o.dual ? 2 : 1)) {
-            HIP_OR_FAIL(c, hipMemcpyAsync(c->d_lens.p + 8 * ngroups_len + 2 * lo, pk->lens + lo, 2 * (size_t)(n - lo),
-                                          hipMemcpyHostToDevice, c->s_in));
+            HIP_TRY(c, hipMemcpyAsync(c->d_lens.p + 8 * ngroups_len + 2 * lo, pk->lens + lo, 2 * (size_t)(n - lo),
+                                      hipMemcpyHostToDevice, c->s_in));
             o.h2d_bytes += 2 * (n - lo);
         }
         if (pk) {
             // the chunk's packed dwords (the caller's bytes only; edge bases are masked)
             const int64_t q0 = std::max((b0 / 16) * 4, o.base0 / 4), q1 = std::min((b1 + 15) / 16 * 4, o.pk_hi);
             if (b1 > b0 && q1 > q0) {
-                HIP_OR_FAIL(c, hipMemcpyAsync(c->d_packed.p + (q0 - o.P0), pk->packed + q0, (size_t)(q1 - q0),
-                                              hipMemcpyHostToDevice, c->s_in));
+                HIP_TRY(c, hipMemcpyAsync(c->d_packed.p + (q0 - o.P0), pk->packed + q0, (size_t)(q1 - q0),
+                                          hipMemcpyHostToDevice, c->s_in));
                 o.h2d_bytes += q1 - q0;
             }
         } else if (b1 > b0) {
-            HIP_OR_FAIL(c, hipMemcpyAsync(c->d_reads.p + (b0 - o.base0), o.reads + b0, (size_t)(b1 - b0),
-                                          hipMemcpyHostToDevice, c->s_in));
+            HIP_TRY(c, hipMemcpyAsync(c->d_reads.p + (b0 - o.base0), o.reads + b0, (size_t)(b1 - b0),
+                                      hipMemcpyHostToDevice, c->s_in));
             o.h2d_bytes += b1 - b0;
         }
         if (!o.lens_on) {
-            HIP_OR_FAIL(c, hipMemcpyAsync(c->d_offsets.p + lo, offsets + lo, sizeof(int64_t) * (size_t)(hi - lo + 1),
-                                          hipMemcpyHostToDevice, c->s_in));
+            HIP_TRY(c, hipMemcpyAsync(c->d_offsets.p + lo, offsets + lo, sizeof(int64_t) * (size_t)(hi - lo + 1),
+                                      hipMemcpyHostToDevice, c->s_in));
             o.h2d_bytes += (int64_t)sizeof(int64_t) * (hi - lo + 1);
         }
-        HIP_OR_FAIL(c, hipEventRecord(c->ev_in[(size_t)k], c->s_in));
+        HIP_TRY(c, hipEventRecord(c->ev_in[(size_t)k], c->s_in));
     }
-    if (o.upload) HIP_OR_FAIL(c, hipEventRecord(c->ev_h1, c->s_in));
+    if (o.upload) HIP_TRY(c, hipEventRecord(c->ev_h1, c->s_in));
     return NW_OK;
 }
 
@@ -2308,7 +2273,7 @@ int prepare_known(nw_ctx* c, OpsCall& o) {
 // small chunks: not kept.)
 int copy_runs(nw_ctx* c, OpsCall& o, int64_t k) {
     o.ht.lap(4);
-    HIP_OR_FAIL(c, hipEventSynchronize(c->ev_ce[(size_t)k]));
+    HIP_TRY(c, hipEventSynchronize(c->ev_ce[(size_t)k]));
     o.ht.lap(5);
     const int64_t* h = c->h_ctl + nw::kOpsCtl * k;
     o.err |= h[nw::kCtlError];
@@ -2318,9 +2283,9 @@ int copy_runs(nw_ctx* c, OpsCall& o, int64_t k) {
     if (!po) {   // records only (a scores-only pass, CORE:1740-1741): the runs stay on the device
     } else if (cb + tot > o.cap_p[pass]) o.cap_short = true;
     else if (tot > 0 && !o.direct_done[(size_t)k])
-        HIP_OR_FAIL(c, hipMemcpyAsync(po + cb, c->sc[k % o.nsets].d_staging.p, sizeof(uint32_t) * (size_t)tot,
-                                      hipMemcpyDeviceToHost, c->s_out));
-    HIP_OR_FAIL(c, hipEventRecord(c->ev_out[(size_t)k], c->s_out));
+        HIP_TRY(c, hipMemcpyAsync(po + cb, c->sc[k % o.nsets].d_staging.p, sizeof(uint32_t) * (size_t)tot,
+                                  hipMemcpyDeviceToHost, c->s_out));
+    HIP_TRY(c, hipEventRecord(c->ev_out[(size_t)k], c->s_out));
     o.total_p[pass] = cb + tot;
     if (po) c->ops_d2h_bytes += 4 * tot;
     return NW_OK;
@@ -2345,11 +2310,11 @@ int run_chunk(nw_ctx* c, OpsCall& o, int64_t k) {
         p.split_to = o.groups ? c->cstream[2] : nullptr;
         p.split_ev = c->ev_bulk[(size_t)k];
         // the set's previous chunk (k - 3) must be through its tail
-        if (k >= nsets) HIP_OR_FAIL(c, hipStreamWaitEvent(p.cs, c->ev_ce[(size_t)(k - nsets)], 0));
+        if (k >= nsets) HIP_TRY(c, hipStreamWaitEvent(p.cs, c->ev_ce[(size_t)(k - nsets)], 0));
     }
-    if (o.upload) HIP_OR_FAIL(c, hipStreamWaitEvent(p.cs, c->ev_in[(size_t)ch.up], 0));
+    if (o.upload) HIP_TRY(c, hipStreamWaitEvent(p.cs, c->ev_in[(size_t)ch.up], 0));
     // (a timing event here sat in every chunk's chain: only with the host timing on)
-    if (o.ht.on) HIP_OR_FAIL(c, hipEventRecord(c->ev_cs[(size_t)k], p.cs));
+    if (o.ht.on) HIP_TRY(c, hipEventRecord(c->ev_cs[(size_t)k], p.cs));
     use_group(c, o, ch.g);
     p.out_off = pass ? o.n + 1 : 0;   // a dual call's pass 1: its records and run offsets after pass 0's
     p.ctl_pass = pass;
@@ -2368,7 +2333,7 @@ int run_chunk(nw_ctx* c, OpsCall& o, int64_t k) {
     // values only (classify's write_read_bytes).
     const bool dual_unpack = pk && o.upload && o.dual && !(o.gcfg[0].use_diag && o.gcfg[1].use_diag);
     if (dual_unpack && pass == 1) {
-        HIP_OR_FAIL(c, hipStreamWaitEvent(p.cs, c->ev_up[(size_t)ch.up], 0));
+        HIP_TRY(c, hipStreamWaitEvent(p.cs, c->ev_up[(size_t)ch.up], 0));
     } else if (pk && o.upload && (!c->ac.use_diag || dual_unpack)) {
         // the exact kernels read bytes: the chunk's bases -> bytes + exceptions
         const int64_t b0 = offsets[lo], b1 = offsets[hi];
@@ -2379,9 +2344,9 @@ int run_chunk(nw_ctx* c, OpsCall& o, int64_t k) {
             lsk = nw::LenSeg{(const uint16_t*)(c->d_lens.p + 8 * o.ngroups_len), (const int64_t*)c->d_lens.p,
                              lo / nw::kLenGroup, hi / nw::kLenGroup - lo / nw::kLenGroup + 1, lo, hi, c->d_offsets.p};
         const nw::LenSeg* ls = o.lens_on ? &lsk : nullptr;
-        HIP_OR_FAIL(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, o.P0, b0, b1, c->d_exc_pos.p, c->d_exc_byte.p,
-                                         e0, e1, c->d_reads.p, c->reads_bias, p.cs, ls));
-        if (dual_unpack) HIP_OR_FAIL(c, hipEventRecord(c->ev_up[(size_t)k], p.cs));
+        HIP_TRY(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, o.P0, b0, b1, c->d_exc_pos.p, c->d_exc_byte.p,
+                                     e0, e1, c->d_reads.p, c->reads_bias, p.cs, ls));
+        if (dual_unpack) HIP_TRY(c, hipEventRecord(c->ev_up[(size_t)k], p.cs));
     }
     if (c->ac.use_diag && ((pk && o.upload) || o.packed_resident)) {
         // band path: classify decodes the chunk from the 2-bit stream itself (rebuilding its
@@ -2461,7 +2426,7 @@ int run_chunk(nw_ctx* c, OpsCall& o, int64_t k) {
                                c->h_ctl + nw::kOpsCtl * k, (int)(o.in_pass(k) & 1), direct_k ? &ho : nullptr)))
         return rc;
     o.direct_done[(size_t)k] = direct_k;
-    HIP_OR_FAIL(c, hipEventRecord(c->ev_ce[(size_t)k], c->last_launch.cs));
+    HIP_TRY(c, hipEventRecord(c->ev_ce[(size_t)k], c->last_launch.cs));
     // s_out order: chunk k - lag's runs (their size is known once that chunk is done:
     // the host waits for it, so lag = nsets - 1 chunks stay queued ahead), then chunk
     // k's records and offsets
@@ -2474,11 +2439,11 @@ int run_chunk(nw_ctx* c, OpsCall& o, int64_t k) {
             o.runs_queued = j + 1;
         }
     if (!direct_k) {
-        HIP_OR_FAIL(c, hipStreamWaitEvent(c->s_out, c->ev_ce[(size_t)k], 0));
-        HIP_OR_FAIL(c, hipMemcpyAsync(o.st_p[pass] + lo, c->d_stats.p + p.out_off + lo,
-                                      sizeof(nw::Stat) * (size_t)(hi - lo), hipMemcpyDeviceToHost, c->s_out));
-        HIP_OR_FAIL(c, hipMemcpyAsync(o.oo_p[pass] + lo, c->d_opsoff.p + p.out_off + lo,
-                                      sizeof(int64_t) * (size_t)(hi - lo), hipMemcpyDeviceToHost, c->s_out));
+        HIP_TRY(c, hipStreamWaitEvent(c->s_out, c->ev_ce[(size_t)k], 0));
+        HIP_TRY(c, hipMemcpyAsync(o.st_p[pass] + lo, c->d_stats.p + p.out_off + lo,
+                                  sizeof(nw::Stat) * (size_t)(hi - lo), hipMemcpyDeviceToHost, c->s_out));
+        HIP_TRY(c, hipMemcpyAsync(o.oo_p[pass] + lo, c->d_opsoff.p + p.out_off + lo,
+                                  sizeof(int64_t) * (size_t)(hi - lo), hipMemcpyDeviceToHost, c->s_out));
     }
     c->ops_d2h_bytes += (int64_t)(sizeof(nw::Stat) + sizeof(int64_t)) * (hi - lo);
     return NW_OK;
@@ -2506,15 +2471,15 @@ int finish_call(nw_ctx* c, OpsCall& o) {
     c->ops_h2d_bytes = o.upload ? o.h2d_bytes : 0;
     if (nchunks > 0) {
         if (o.upload)
-            HIP_OR_FAIL(c, hipEventElapsedTime(&c->ops_h2d_ms, c->ev_h0, c->ev_h1));
+            HIP_TRY(c, hipEventElapsedTime(&c->ops_h2d_ms, c->ev_h0, c->ev_h1));
         // the chunks' compute spans summed (host timing on: their start events), else the call's device
         // span, first upload to the last chunk's end
         for (int64_t k = 0; k < nchunks; ++k) {
             float ms = 0.0f;
-            if (o.ht.on) HIP_OR_FAIL(c, hipEventElapsedTime(&ms, c->ev_cs[(size_t)k], c->ev_ce[(size_t)k]));
+            if (o.ht.on) HIP_TRY(c, hipEventElapsedTime(&ms, c->ev_cs[(size_t)k], c->ev_ce[(size_t)k]));
             c->ops_compute_ms += ms;
         }
-        if (!o.ht.on) HIP_OR_FAIL(c, hipEventElapsedTime(&c->ops_compute_ms, c->ev_h0, c->ev_ce[(size_t)nchunks - 1]));
+        if (!o.ht.on) HIP_TRY(c, hipEventElapsedTime(&c->ops_compute_ms, c->ev_h0, c->ev_ce[(size_t)nchunks - 1]));
         for (size_t i = 0; i < c->call.trace_used; ++i) {
             float t = 0;
             (void)hipEventElapsedTime(&t, c->ev_h0, c->trace_ev[i].second);
@@ -2642,7 +2607,7 @@ int ops_call(nw_ctx* c, const Switches& sw, const char* reads, const int64_t* of
     // sweep only lengthened each chain: removed, in-process A/Bs C2 call 1.894 -> 1.833 ms, resident
     // pass 0.536 -> 0.484 ms, dual call 5.28 -> 5.12 ms, C1 shape 3.03 -> 2.98 ms)
     if (rc) return drain(c, rc);
-    HIP_OR_FAIL(c, hipMemsetAsync(c->d_ctl64.p, 0, 2 * nw::kOpsCtlAll * sizeof(int64_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_ctl64.p, 0, 2 * nw::kOpsCtlAll * sizeof(int64_t), c->stream));
     if ((rc = prepare_known(c, o))) return rc;
     // The last chunk's records, offsets and runs are written by its compaction kernel straight
     // into the caller's buffers when they are page-locked: no copies and no host round trip
@@ -2665,19 +2630,19 @@ int ops_call(nw_ctx* c, const Switches& sw, const char* reads, const int64_t* of
     // need its bytes, unpacked once here before any chunk
     o.packed_resident = !upload && c->resident_packed && c->ac.use_diag;
     if (!upload && c->resident_packed && !c->ac.use_diag && n > 0)
-        HIP_OR_FAIL(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, o.P0, o.base0, o.base0 + o.nbytes, c->d_exc_pos.p,
-                                         c->d_exc_byte.p, 0, c->resident_n_exc, c->d_reads.p, c->reads_bias, c->stream));
+        HIP_TRY(c, nw::launch_unpack((const uint32_t*)c->d_packed.p, o.P0, o.base0, o.base0 + o.nbytes, c->d_exc_pos.p,
+                                     c->d_exc_byte.p, 0, c->resident_n_exc, c->d_reads.p, c->reads_bias, c->stream));
     // the ctl reset and the exceptions' upload are on the first compute stream and s_in:
     // both compute streams start after them
-    HIP_OR_FAIL(c, hipEventRecord(c->ev_start, c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev_start, c->stream));
     for (int k = 1; k < std::min(o.nsets, kComputeStreams); ++k)
-        HIP_OR_FAIL(c, hipStreamWaitEvent(c->cstream[k], c->ev_start, 0));
+        HIP_TRY(c, hipStreamWaitEvent(c->cstream[k], c->ev_start, 0));
     for (int64_t k = 0; k < nchunks; ++k)
         if ((rc = run_chunk(c, o, k))) return rc;
     for (int64_t k = std::max<int64_t>(o.runs_queued, nchunks - o.lag); k < nchunks; ++k)
         if ((rc = copy_runs(c, o, k))) return rc;
     o.ht.lap(4);
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->s_out));
+    HIP_TRY(c, hipStreamSynchronize(c->s_out));
     o.ht.lap(6);
     ops_off[n] = o.total_p[0];
     if (dual) dual->ops_off2[n] = o.total_p[1];
@@ -2944,19 +2909,19 @@ int nw_batch_phase_times(nw_ctx* c, float* ms5) {
     if (!c || !ms5) return NW_E_INVALID;
     if (!c->ran) return fail(c, NW_E_STATE, "nothing has run");
     (void)hipSetDevice(c->device);
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < 5; ++k) ms5[k] = 0.0f;
     if (!c->phases_recorded) return fail(c, NW_E_STATE, "the last run recorded no phase events (nw_batch_set_phase_events)");
     if (!c->ac.use_diag || c->n <= 0) {
-        HIP_OR_FAIL(c, hipEventElapsedTime(&ms5[4], c->ev0, c->ev1));
+        HIP_TRY(c, hipEventElapsedTime(&ms5[4], c->ev0, c->ev1));
         return NW_OK;
     }
     const bool two = c->ac.diag16_fill.grid > 0;
-    HIP_OR_FAIL(c, hipEventElapsedTime(&ms5[0], c->ev0, c->ev_sort));
-    HIP_OR_FAIL(c, hipEventElapsedTime(&ms5[1], c->ev_sort, c->ev_fill));
-    HIP_OR_FAIL(c, hipEventElapsedTime(&ms5[2], c->ev_fill, c->ev_walk));
-    HIP_OR_FAIL(c, hipEventElapsedTime(&ms5[3], c->ev_walk, c->ev_l2));
-    HIP_OR_FAIL(c, hipEventElapsedTime(&ms5[4], c->ev_l2, c->ev1));
+    HIP_TRY(c, hipEventElapsedTime(&ms5[0], c->ev0, c->ev_sort));
+    HIP_TRY(c, hipEventElapsedTime(&ms5[1], c->ev_sort, c->ev_fill));
+    HIP_TRY(c, hipEventElapsedTime(&ms5[2], c->ev_fill, c->ev_walk));
+    HIP_TRY(c, hipEventElapsedTime(&ms5[3], c->ev_walk, c->ev_l2));
+    HIP_TRY(c, hipEventElapsedTime(&ms5[4], c->ev_l2, c->ev1));
     if (!two) {   // one level: ms5[1..2] are the 32-diagonal level's, ms5[3] is empty
         ms5[3] = 0.0f;
     }
@@ -2971,14 +2936,14 @@ int nw_batch_path_counts(nw_ctx* c, int64_t* counts4) {
     }
     if (!c->ran) return fail(c, NW_E_STATE, "nothing has run");
     (void)hipSetDevice(c->device);
-    HIP_OR_FAIL(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     for (int k = 0; k < 4; ++k) counts4[k] = 0;
     if (!c->ac.use_diag) {
         counts4[3] = nw_batch_fallbacks(c);
         return NW_OK;
     }
     int32_t fb[nw::kChunkCounters] = {}, need = 0;
-    HIP_OR_FAIL(c, hipMemcpy(fb, c->sc[0].d_fallback_count.p, sizeof fb, hipMemcpyDeviceToHost));
+    HIP_TRY(c, hipMemcpy(fb, c->sc[0].d_fallback_count.p, sizeof fb, hipMemcpyDeviceToHost));
     need = fb[nw::kCntDp];
     const bool two = c->ac.diag16_fill.grid > 0;
     counts4[0] = c->n - need;             // exact copies (no DP)

@@ -23,7 +23,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -32,6 +31,7 @@
 
 #include "../../include/crispr_nw.h"
 #include "../../include/crispr_quant.h"
+#include "host_dev.h"
 #include "nw_common.h"
 #include "nw_edna.h"
 
@@ -910,26 +910,6 @@ __global__ void quant_reduce(const uint32_t* __restrict__ partial, int nblocks, 
 
 namespace {
 
-template <class T>
-struct QBuf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap) return hipSuccess;
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 constexpr int kMaxLds = 160 * 1024;
 
 }  // namespace
@@ -946,17 +926,17 @@ struct nwq_ctx {
     int32_t window = 0;
     int64_t lane_fallbacks = -1;     // the last nwq_run_device_ops' quant_lanes fallback count
     std::vector<int32_t> prefix;     // host copy of QArgs::prefix
-    QBuf<int32_t> d_prefix;
-    QBuf<uint32_t> d_partial;
-    QBuf<int64_t> d_totals;
-    QBuf<uint8_t> d_aln, d_pre;
-    QBuf<int32_t> d_len;
-    QBuf<nwq_read> d_out;
+    hd::DevBuf<int32_t> d_prefix;
+    hd::DevBuf<uint32_t> d_partial;
+    hd::DevBuf<int64_t> d_totals;
+    hd::DevBuf<uint8_t> d_aln, d_pre;
+    hd::DevBuf<int32_t> d_len;
+    hd::DevBuf<nwq_read> d_out;
     // nwq_run_device_ops: the amplicon, its positive-code masks, ascii -> EDNAFULL code
-    QBuf<uint8_t> d_amp, d_lut;
-    QBuf<uint32_t> d_rowpos;
+    hd::DevBuf<uint8_t> d_amp, d_lut;
+    hd::DevBuf<uint32_t> d_rowpos;
     std::string amp_key;
-    QBuf<int32_t> d_fb;      // quant_lanes' fallback list [n] + its count
+    hd::DevBuf<int32_t> d_fb;      // quant_lanes' fallback list [n] + its count
     bool rows_only = false;  // CRISPR_NWQ_ROWS=1: every read through the rows (A/B, tests)
     // page-locked landing space of the call's results (the totals, the fallback count): copied back on
     // the stream before its one synchronisation, no pageable staging or second round trip
@@ -983,21 +963,7 @@ int occupancy(nwq_ctx* c, const void* f, int threads, int lds, int* per_cu) {
     return 0;
 }
 
-int qfail(nwq_ctx* c, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
-}
-
-#define QHIP(c, expr)                                                                            \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess) return qfail((c), NW_E_HIP, "%s: %s", #expr, hipGetErrorString(e_)); \
-    } while (0)
+using hd::fail;
 
 int64_t hist_size(int32_t LEN, int64_t stride) { return (int64_t)LEN + stride + 1; }
 int64_t words_for(int32_t LEN, int64_t stride) { return (int64_t)nwq::NV * LEN + 4 + 2 * hist_size(LEN, stride); }
@@ -1024,10 +990,10 @@ int geometry(nwq_ctx* c, int64_t stride, int64_t n, QGeom* g) {
         }
     }
     if (!g->wpb)
-        return qfail(c, NW_E_UNSUPPORTED, "quantification state for amplicon length %d / stride %lld exceeds LDS",
-                     LEN, (long long)stride);
+        return fail(c, NW_E_UNSUPPORTED, "quantification state for amplicon length %d / stride %lld exceeds LDS",
+                    LEN, (long long)stride);
     int per_cu = 0;
-    QHIP(c, (hipError_t)occupancy(c, (const void*)nwq::quant_kernel, 64 * g->wpb, g->lds, &per_cu));
+    HIP_TRY(c, (hipError_t)occupancy(c, (const void*)nwq::quant_kernel, 64 * g->wpb, g->lds, &per_cu));
     per_cu = std::max(per_cu, 1);
     const int64_t need = (n + g->wpb - 1) / g->wpb;
     g->grid = (int)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)c->num_cus * per_cu));
@@ -1041,16 +1007,16 @@ int run_impl(nwq_ctx* c, uint8_t* d_aln, int64_t stride, const int32_t* d_len, i
              const uint8_t* d_pre, int64_t n, nwq_read* d_out, int64_t* totals, float* kernel_ms,
              bool started = false, const int32_t* list = nullptr, const int32_t* list_count = nullptr,
              int slabs0 = 0, int32_t* nfb = nullptr) {
-    if (!c->have_params) return qfail(c, NW_E_STATE, "nwq_set_params not called");
+    if (!c->have_params) return fail(c, NW_E_STATE, "nwq_set_params not called");
     if (stride <= 0 || (stride & 3) || stride >= 32768)
-        return qfail(c, NW_E_INVALID, "stride %lld must be a positive multiple of 4 below 32768", (long long)stride);
-    if (n < 0) return qfail(c, NW_E_INVALID, "negative read count");
+        return fail(c, NW_E_INVALID, "stride %lld must be a positive multiple of 4 below 32768", (long long)stride);
+    if (n < 0) return fail(c, NW_E_INVALID, "negative read count");
     QGeom g;
     int rc = geometry(c, stride, n, &g);
     if (rc) return rc;
     if (list) g.grid = std::min(g.grid, c->num_cus);   // a short list (usually empty): a small grid
-    QHIP(c, c->d_partial.reserve((size_t)(slabs0 + g.grid) * g.nwords));
-    QHIP(c, c->d_totals.reserve((size_t)g.nwords));
+    HIP_TRY(c, c->d_partial.reserve((size_t)(slabs0 + g.grid) * g.nwords));
+    HIP_TRY(c, c->d_totals.reserve((size_t)g.nwords));
     nwq::QArgs a;
     a.aln = d_aln;
     a.stride = stride;
@@ -1071,30 +1037,30 @@ int run_impl(nwq_ctx* c, uint8_t* d_aln, int64_t stride, const int32_t* d_len, i
     a.wave_words = g.wave_words;
     a.base_words = g.base_words;
     a.flags = c->flags;
-    if (!started) QHIP(c, hipEventRecord(c->ev0, c->stream));   // (the row expansion records it first)
+    if (!started) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));   // (the row expansion records it first)
     hipLaunchKernelGGL(nwq::quant_kernel, dim3(g.grid), dim3(64 * g.wpb), g.lds, c->stream, a);
-    QHIP(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     const int nslabs = slabs0 + g.grid;
     const int slices = std::min(nslabs, 32), slice = (nslabs + slices - 1) / slices;
-    QHIP(c, hipMemsetAsync(c->d_totals.p, 0, sizeof(int64_t) * (size_t)g.nwords, c->stream));
+    HIP_TRY(c, hipMemsetAsync(c->d_totals.p, 0, sizeof(int64_t) * (size_t)g.nwords, c->stream));
     hipLaunchKernelGGL(nwq::quant_reduce, dim3((g.nwords + 255) / 256, slices), dim3(256), 0, c->stream,
                        c->d_partial.p, nslabs, g.nwords, slice, reinterpret_cast<unsigned long long*>(c->d_totals.p));
-    QHIP(c, hipGetLastError());
-    QHIP(c, hipEventRecord(c->ev1, c->stream));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev1, c->stream));
     if (c->h_totals_cap < g.nwords) {
         if (c->h_totals) (void)hipHostFree(c->h_totals);
         c->h_totals = nullptr;
         c->h_totals_cap = 0;
-        QHIP(c, hipHostMalloc((void**)&c->h_totals, sizeof(int64_t) * (size_t)g.nwords, hipHostMallocDefault));
+        HIP_TRY(c, hipHostMalloc((void**)&c->h_totals, sizeof(int64_t) * (size_t)g.nwords, hipHostMallocDefault));
         c->h_totals_cap = g.nwords;
     }
-    QHIP(c, hipMemcpyAsync(c->h_totals, c->d_totals.p, sizeof(int64_t) * (size_t)g.nwords, hipMemcpyDeviceToHost,
-                           c->stream));
-    if (nfb && list_count) QHIP(c, hipMemcpyAsync(c->h_nfb, list_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-    QHIP(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->h_totals, c->d_totals.p, sizeof(int64_t) * (size_t)g.nwords, hipMemcpyDeviceToHost,
+                              c->stream));
+    if (nfb && list_count) HIP_TRY(c, hipMemcpyAsync(c->h_nfb, list_count, sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     std::memcpy(totals, c->h_totals, sizeof(int64_t) * (size_t)g.nwords);
     if (nfb && list_count) *nfb = *c->h_nfb;
-    if (kernel_ms) QHIP(c, hipEventElapsedTime(kernel_ms, c->ev0, c->ev1));
+    if (kernel_ms) HIP_TRY(c, hipEventElapsedTime(kernel_ms, c->ev0, c->ev1));
     return NW_OK;
 }
 
@@ -1127,17 +1093,6 @@ int nwq_create(int device, nwq_ctx** out) {
 void nwq_destroy(nwq_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
-    c->d_prefix.release();
-    c->d_partial.release();
-    c->d_totals.release();
-    c->d_aln.release();
-    c->d_pre.release();
-    c->d_len.release();
-    c->d_out.release();
-    c->d_amp.release();
-    c->d_lut.release();
-    c->d_rowpos.release();
-    c->d_fb.release();
     if (c->h_totals) (void)hipHostFree(c->h_totals);
     if (c->h_nfb) (void)hipHostFree(c->h_nfb);
     if (c->ev0) (void)hipEventDestroy(c->ev0);
@@ -1151,9 +1106,9 @@ const char* nwq_last_error(const nwq_ctx* c) { return c ? c->err.c_str() : "null
 int nwq_set_params(nwq_ctx* c, const nwq_params* p) {
     if (!c || !p) return NW_E_INVALID;
     const int LEN = p->len_amplicon;
-    if (LEN <= 0 || LEN >= 32768) return qfail(c, NW_E_INVALID, "len_amplicon %d out of range (1..32767)", LEN);
-    if (!p->include_mask) return qfail(c, NW_E_INVALID, "include_mask is required");
-    if (hipSetDevice(c->device) != hipSuccess) return qfail(c, NW_E_HIP, "hipSetDevice failed");
+    if (LEN <= 0 || LEN >= 32768) return fail(c, NW_E_INVALID, "len_amplicon %d out of range (1..32767)", LEN);
+    if (!p->include_mask) return fail(c, NW_E_INVALID, "include_mask is required");
+    if (hipSetDevice(c->device) != hipSuccess) return fail(c, NW_E_HIP, "hipSetDevice failed");
     const int pref_words = 3 * (LEN + 1) + (LEN + 3) / 4;
     c->prefix.assign((size_t)pref_words, 0);
     int32_t* inc = c->prefix.data();
@@ -1169,8 +1124,8 @@ int nwq_set_params(nwq_ctx* c, const nwq_params* p) {
         exo[i + 1] = exo[i] + be;
         spl[i + 1] = spl[i] + bs;
     }
-    QHIP(c, c->d_prefix.reserve((size_t)pref_words));
-    QHIP(c, hipMemcpy(c->d_prefix.p, c->prefix.data(), sizeof(int32_t) * (size_t)pref_words, hipMemcpyHostToDevice));
+    HIP_TRY(c, c->d_prefix.reserve((size_t)pref_words));
+    HIP_TRY(c, hipMemcpy(c->d_prefix.p, c->prefix.data(), sizeof(int32_t) * (size_t)pref_words, hipMemcpyHostToDevice));
     c->LEN = LEN;
     c->window = p->window_around_sgrna;
     c->flags = (p->ignore_substitutions ? nwq::F_IGN_SUB : 0) | (p->ignore_insertions ? nwq::F_IGN_INS : 0) |
@@ -1187,26 +1142,26 @@ int64_t nwq_totals_words(const nwq_ctx* c, int64_t stride) {
 int nwq_run(nwq_ctx* c, uint8_t* aln, int64_t stride, const int32_t* aln_len, const uint8_t* pre, int64_t n,
             nwq_read* out, int64_t* totals, float* kernel_ms) {
     if (!c) return NW_E_INVALID;
-    if (n > 0 && (!aln || !aln_len || !pre || !out)) return qfail(c, NW_E_INVALID, "null buffer");
-    if (!totals) return qfail(c, NW_E_INVALID, "null totals");
-    QHIP(c, hipSetDevice(c->device));
+    if (n > 0 && (!aln || !aln_len || !pre || !out)) return fail(c, NW_E_INVALID, "null buffer");
+    if (!totals) return fail(c, NW_E_INVALID, "null totals");
+    HIP_TRY(c, hipSetDevice(c->device));
     const size_t nn = (size_t)std::max<int64_t>(n, 1);
-    QHIP(c, c->d_aln.reserve(nn * 3 * (size_t)stride));
-    QHIP(c, c->d_len.reserve(nn));
-    QHIP(c, c->d_pre.reserve(nn));
-    QHIP(c, c->d_out.reserve(nn));
+    HIP_TRY(c, c->d_aln.reserve(nn * 3 * (size_t)stride));
+    HIP_TRY(c, c->d_len.reserve(nn));
+    HIP_TRY(c, c->d_pre.reserve(nn));
+    HIP_TRY(c, c->d_out.reserve(nn));
     if (n > 0) {
-        QHIP(c, hipMemcpyAsync(c->d_aln.p, aln, (size_t)n * 3 * stride, hipMemcpyHostToDevice, c->stream));
-        QHIP(c, hipMemcpyAsync(c->d_len.p, aln_len, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-        QHIP(c, hipMemcpyAsync(c->d_pre.p, pre, (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_aln.p, aln, (size_t)n * 3 * stride, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_len.p, aln_len, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_pre.p, pre, (size_t)n, hipMemcpyHostToDevice, c->stream));
     }
     int rc = run_impl(c, c->d_aln.p, stride, c->d_len.p, 1, c->d_pre.p, n, c->d_out.p, totals, kernel_ms);
     if (rc) return rc;
     if (n > 0) {
-        QHIP(c, hipMemcpy(out, c->d_out.p, sizeof(nwq_read) * (size_t)n, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(out, c->d_out.p, sizeof(nwq_read) * (size_t)n, hipMemcpyDeviceToHost));
         if (c->flags & nwq::F_NFIX)
-            QHIP(c, hipMemcpy2D(aln + stride, (size_t)(3 * stride), c->d_aln.p + stride, (size_t)(3 * stride),
-                                (size_t)stride, (size_t)n, hipMemcpyDeviceToHost));
+            HIP_TRY(c, hipMemcpy2D(aln + stride, (size_t)(3 * stride), c->d_aln.p + stride, (size_t)(3 * stride),
+                                   (size_t)stride, (size_t)n, hipMemcpyDeviceToHost));
     }
     return NW_OK;
 }
@@ -1214,10 +1169,10 @@ int nwq_run(nwq_ctx* c, uint8_t* aln, int64_t stride, const int32_t* aln_len, co
 int nwq_run_device(nwq_ctx* c, uint8_t* d_aln, int64_t stride, const int32_t* d_aln_len, int64_t len_stride,
                    const uint8_t* d_pre, int64_t n, nwq_read* d_out, int64_t* totals, float* kernel_ms) {
     if (!c) return NW_E_INVALID;
-    if (n > 0 && (!d_aln || !d_aln_len || !d_pre || !d_out)) return qfail(c, NW_E_INVALID, "null buffer");
-    if (!totals) return qfail(c, NW_E_INVALID, "null totals");
-    if (len_stride <= 0) return qfail(c, NW_E_INVALID, "len_stride must be positive");
-    QHIP(c, hipSetDevice(c->device));
+    if (n > 0 && (!d_aln || !d_aln_len || !d_pre || !d_out)) return fail(c, NW_E_INVALID, "null buffer");
+    if (!totals) return fail(c, NW_E_INVALID, "null totals");
+    if (len_stride <= 0) return fail(c, NW_E_INVALID, "len_stride must be positive");
+    HIP_TRY(c, hipSetDevice(c->device));
     return run_impl(c, d_aln, stride, d_aln_len, len_stride, d_pre, n, d_out, totals, kernel_ms);
 }
 
@@ -1226,15 +1181,15 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
                        int64_t reads_bias, int64_t stride, const uint8_t* d_pre, int64_t n, nwq_read* d_out,
                        int64_t* totals, float* kernel_ms) {
     if (!c) return NW_E_INVALID;
-    if (!c->have_params) return qfail(c, NW_E_STATE, "nwq_set_params not called");
+    if (!c->have_params) return fail(c, NW_E_STATE, "nwq_set_params not called");
     if (!amplicon || amplicon_len != c->LEN)
-        return qfail(c, NW_E_INVALID, "amplicon of %d bases for len_amplicon %d", amplicon_len, c->LEN);
+        return fail(c, NW_E_INVALID, "amplicon of %d bases for len_amplicon %d", amplicon_len, c->LEN);
     if (n > 0 && (!d_ops || !d_ops_off || !d_stats || !d_reads || !d_offsets || !d_pre || !d_out))
-        return qfail(c, NW_E_INVALID, "null buffer");
-    if (!totals) return qfail(c, NW_E_INVALID, "null totals");
+        return fail(c, NW_E_INVALID, "null buffer");
+    if (!totals) return fail(c, NW_E_INVALID, "null totals");
     if (stride <= 0 || (stride & 3) || stride >= 32768)
-        return qfail(c, NW_E_INVALID, "stride %lld must be a positive multiple of 4 below 32768", (long long)stride);
-    QHIP(c, hipSetDevice(c->device));
+        return fail(c, NW_E_INVALID, "stride %lld must be a positive multiple of 4 below 32768", (long long)stride);
+    HIP_TRY(c, hipSetDevice(c->device));
     const std::string key(amplicon, amplicon + amplicon_len);
     if (key != c->amp_key) {   // the amplicon's tables (the markup's ':' test), once per amplicon
         std::vector<uint32_t> rowpos((size_t)amplicon_len);
@@ -1247,16 +1202,16 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
                 if (ca < 16 && nw::kEdna[ca][code] > 0) m |= 1u << code;
             rowpos[(size_t)i] = m;
         }
-        QHIP(c, c->d_amp.reserve((size_t)amplicon_len + 16));
-        QHIP(c, c->d_rowpos.reserve((size_t)amplicon_len));
-        QHIP(c, c->d_lut.reserve(256));
-        QHIP(c, hipMemcpy(c->d_amp.p, amplicon, (size_t)amplicon_len, hipMemcpyHostToDevice));
-        QHIP(c, hipMemcpy(c->d_rowpos.p, rowpos.data(), 4 * rowpos.size(), hipMemcpyHostToDevice));
-        QHIP(c, hipMemcpy(c->d_lut.p, lut.data(), 256, hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_amp.reserve((size_t)amplicon_len + 16));
+        HIP_TRY(c, c->d_rowpos.reserve((size_t)amplicon_len));
+        HIP_TRY(c, c->d_lut.reserve(256));
+        HIP_TRY(c, hipMemcpy(c->d_amp.p, amplicon, (size_t)amplicon_len, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_rowpos.p, rowpos.data(), 4 * rowpos.size(), hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_lut.p, lut.data(), 256, hipMemcpyHostToDevice));
         c->amp_key = key;
     }
     const size_t nn = (size_t)std::max<int64_t>(n, 1);
-    QHIP(c, c->d_aln.reserve(nn * 3 * (size_t)stride));
+    HIP_TRY(c, c->d_aln.reserve(nn * 3 * (size_t)stride));
     // the lane path (quant_lanes: features straight from the runs) for an amplicon of A C G T
     // without the N rule, when its LDS fits; its fallback reads (and every read otherwise) go
     // through the rows rebuilt on the device
@@ -1272,20 +1227,20 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
     while (lane_wpb > 1 && 4 * (base_words + amp_words + lane_wpb * nwq::kQWaveWords) > kMaxLds / 2) lane_wpb >>= 1;
     const int lane_lds = 4 * (base_words + amp_words + lane_wpb * nwq::kQWaveWords);
     const bool lanes = acgt && !(c->flags & nwq::F_NFIX) && lane_lds <= kMaxLds && n > 0 && !c->rows_only;
-    QHIP(c, hipEventRecord(c->ev0, c->stream));   // kernel_ms covers the expansion too
+    HIP_TRY(c, hipEventRecord(c->ev0, c->stream));   // kernel_ms covers the expansion too
     c->lane_fallbacks = -1;
     if (lanes) {
         int per_cu = 0;
-        QHIP(c, (hipError_t)occupancy(c, (const void*)nwq::quant_lanes, 64 * lane_wpb, lane_lds, &per_cu));
+        HIP_TRY(c, (hipError_t)occupancy(c, (const void*)nwq::quant_lanes, 64 * lane_wpb, lane_lds, &per_cu));
         per_cu = std::max(per_cu, 1);
         const int64_t groups = (n + nwq::kQSuper - 1) / nwq::kQSuper;   // a wave's super-groups
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((groups + lane_wpb - 1) / lane_wpb,
                                                                      (int64_t)c->num_cus * per_cu));
-        QHIP(c, c->d_fb.reserve(nn + 1));
+        HIP_TRY(c, c->d_fb.reserve(nn + 1));
         // every slab up front: the row kernel's list grid is at most num_cus (run_impl), and a
         // reserve there would move the slabs this kernel is about to write
-        QHIP(c, c->d_partial.reserve((size_t)(grid + c->num_cus) * nwords));
-        QHIP(c, hipMemsetAsync(c->d_fb.p + nn, 0, sizeof(int32_t), c->stream));
+        HIP_TRY(c, c->d_partial.reserve((size_t)(grid + c->num_cus) * nwords));
+        HIP_TRY(c, hipMemsetAsync(c->d_fb.p + nn, 0, sizeof(int32_t), c->stream));
         nwq::LArgs la;
         la.ops = d_ops;
         la.ops_off = d_ops_off;
@@ -1312,16 +1267,16 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
         la.amp_words = amp_words;
         la.flags = c->flags;
         hipLaunchKernelGGL(nwq::quant_lanes, dim3(grid), dim3(64 * lane_wpb), lane_lds, c->stream, la);
-        QHIP(c, hipGetLastError());
+        HIP_TRY(c, hipGetLastError());
         // the fallback reads: their rows, then the row kernel over the list
         int wpb = 4;
         while (wpb > 1 && (int64_t)wpb * 3 * stride > 64 * 1024) wpb >>= 1;
         const int lds = (int)(wpb * 3 * stride);
-        if (lds > kMaxLds) return qfail(c, NW_E_UNSUPPORTED, "stride %lld too long for the row expansion", (long long)stride);
+        if (lds > kMaxLds) return fail(c, NW_E_UNSUPPORTED, "stride %lld too long for the row expansion", (long long)stride);
         hipLaunchKernelGGL(nwq::expand_rows, dim3(c->num_cus), dim3(64 * wpb), lds, c->stream, d_ops, d_ops_off,
                            (const int32_t*)d_stats, d_reads, d_offsets, reads_bias, c->d_amp.p, c->d_rowpos.p,
                            c->d_lut.p, amplicon_len, d_pre, 0, n, c->d_aln.p, stride, c->d_fb.p, c->d_fb.p + nn);
-        QHIP(c, hipGetLastError());
+        HIP_TRY(c, hipGetLastError());
         int32_t nfb = -1;
         const int rc = run_impl(c, c->d_aln.p, stride, (const int32_t*)d_stats, 8, d_pre, n, d_out, totals, kernel_ms,
                                 true, c->d_fb.p, c->d_fb.p + nn, grid, &nfb);
@@ -1332,13 +1287,13 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
         int wpb = 4;
         while (wpb > 1 && (int64_t)wpb * 3 * stride > 64 * 1024) wpb >>= 1;
         const int lds = (int)(wpb * 3 * stride);
-        if (lds > kMaxLds) return qfail(c, NW_E_UNSUPPORTED, "stride %lld too long for the row expansion", (long long)stride);
+        if (lds > kMaxLds) return fail(c, NW_E_UNSUPPORTED, "stride %lld too long for the row expansion", (long long)stride);
         const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + wpb - 1) / wpb, (int64_t)c->num_cus * 16));
         hipLaunchKernelGGL(nwq::expand_rows, dim3(grid), dim3(64 * wpb), lds, c->stream, d_ops, d_ops_off,
                            (const int32_t*)d_stats, d_reads, d_offsets, reads_bias, c->d_amp.p, c->d_rowpos.p,
                            c->d_lut.p, amplicon_len, d_pre, (int)((c->flags & nwq::F_NFIX) != 0), n, c->d_aln.p,
                            stride, nullptr, nullptr);
-        QHIP(c, hipGetLastError());
+        HIP_TRY(c, hipGetLastError());
     }
     // the records' aln_len, 8 ints apart (nw_stat)
     return run_impl(c, c->d_aln.p, stride, (const int32_t*)d_stats, 8, d_pre, n, d_out, totals, kernel_ms, true);

@@ -43,7 +43,6 @@
 
 #include <algorithm>
 #include <chrono>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -53,6 +52,8 @@
 
 #include "../../include/crispr_nw.h"
 #include "../../include/crispr_regions.h"
+#include "group_device.h"
+#include "host_dev.h"
 #include "nw_bam.h"
 
 namespace nwr {
@@ -390,15 +391,9 @@ __global__ __launch_bounds__(kBlk) void nwr_span_kernel(const SpanArgs a) {
 // at most are written.
 __global__ __launch_bounds__(kBlk) void nwr_compact_kernel(const Table t, Listed* list, uint64_t cap,
                                                            unsigned long long* ctr) {
-    const int lane = threadIdx.x & 63;
     const uint64_t s = (uint64_t)blockIdx.x * kBlk + threadIdx.x;
     const bool used = s <= t.cap_mask && t.w1[s] != 0;
-    const unsigned long long b = __ballot(used);
-    if (!b) return;
-    const int lead = __ffsll((long long)b) - 1;
-    unsigned long long at = 0;
-    if (lane == lead) at = atomicAdd(&ctr[kListed], (unsigned long long)__popcll(b));
-    at = __shfl(at, lead, 64) + (unsigned long long)__popcll(b & ((1ull << lane) - 1ull));
+    const unsigned long long at = grp::wave_reserve(used, &ctr[kListed]);
     if (used && at < cap) list[at] = Listed{t.w0[s], t.w1[s] - 1, (uint32_t)s, t.count[s]};
 }
 
@@ -492,24 +487,6 @@ __global__ __launch_bounds__(256) void nwr_emit_kernel(const uint8_t* data, cons
     quals[t] = qw;
 }
 
-template <class T>
-struct Buf {
-    T* p = nullptr;
-    size_t cap = 0;
-    hipError_t reserve(size_t n) {
-        if (n <= cap && p) return hipSuccess;
-        release();
-        hipError_t e = hipMalloc((void**)&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e == hipSuccess) cap = n;
-        return e;
-    }
-    void release() {
-        if (p) (void)hipFree(p);
-        p = nullptr;
-        cap = 0;
-    }
-};
-
 // The hits of one chunk (or of the whole call) in region-major order.
 struct Hits {
     std::vector<int32_t> reg, st, en;
@@ -529,46 +506,26 @@ struct Result {
 
 }  // namespace nwr
 
-struct nwr_ctx {
-    int device = 0;
+struct nwr_ctx : hd::DevContext {
     int64_t chunk_records = 0;      // 0: by bytes
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {};
-    std::string err;
-    nwr::Buf<uint8_t> d_data;
-    nwr::Buf<int64_t> d_off, d_rstart, d_rend;
-    nwr::Buf<int32_t> d_rref;
-    nwr::Buf<uint32_t> d_counts, d_sums, d_ooff, d_text, d_quals;
-    nwr::Buf<unsigned long long> d_totals;
-    nwr::Buf<uint4> d_hits;
-    nwr::Buf<nwr::EmitHit> d_eh;
+    hd::DevBuf<uint8_t> d_data;
+    hd::DevBuf<int64_t> d_off, d_rstart, d_rend;
+    hd::DevBuf<int32_t> d_rref;
+    hd::DevBuf<uint32_t> d_counts, d_sums, d_ooff, d_text, d_quals;
+    hd::DevBuf<unsigned long long> d_totals;
+    hd::DevBuf<uint4> d_hits;
+    hd::DevBuf<nwr::EmitHit> d_eh;
     // nwr_discover
     int hash_bits = 64;             // CRISPR_NWR_HASH_BITS
-    nwr::Buf<unsigned long long> d_w0, d_w1, d_ctr;
-    nwr::Buf<uint32_t> d_tcount, d_slot, d_lslot;
-    nwr::Buf<int32_t> d_map, d_lreg;
-    nwr::Buf<nwr::Listed> d_list;
+    hd::DevBuf<unsigned long long> d_w0, d_w1, d_ctr;
+    hd::DevBuf<uint32_t> d_tcount, d_slot, d_lslot;
+    hd::DevBuf<int32_t> d_map, d_lreg;
+    hd::DevBuf<nwr::Listed> d_list;
 };
 
 namespace {
 
-int rfail(nwr_ctx* c, int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    std::vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (c) c->err = buf;
-    return code;
-}
-
-#define RHIP(c, expr)                                                                             \
-    do {                                                                                          \
-        hipError_t e_ = (expr);                                                                   \
-        if (e_ != hipSuccess)                                                                     \
-            return rfail((c), e_ == hipErrorOutOfMemory ? NW_E_NOMEM : NW_E_HIP, "%s: %s", #expr, \
-                         hipGetErrorString(e_));                                                  \
-    } while (0)
+using hd::fail;
 
 inline uint32_t h16(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8); }
 inline uint32_t h32(const uint8_t* p) { return h16(p) | (h16(p + 2) << 16); }
@@ -593,13 +550,13 @@ int upload_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, bool of
     off->resize((size_t)cn + 1);
     for (int64_t i = 0; i <= cn; ++i) (*off)[(size_t)i] = bam->off[(size_t)(r0 + i)] - base;
     if (!upload_ms) return NW_OK;      // (the records are in d_data already)
-    RHIP(c, c->d_data.reserve((size_t)nbytes));
-    RHIP(c, c->d_off.reserve((size_t)cn + 1));
+    HIP_TRY(c, c->d_data.reserve((size_t)nbytes));
+    HIP_TRY(c, c->d_off.reserve((size_t)cn + 1));
     const auto t0 = std::chrono::steady_clock::now();
-    RHIP(c, hipMemcpyAsync(c->d_data.p, bam->data.data() + base, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(c->d_data.p, bam->data.data() + base, (size_t)nbytes, hipMemcpyHostToDevice, c->stream));
     if (offsets_too)
-        RHIP(c, hipMemcpyAsync(c->d_off.p, off->data(), sizeof(int64_t) * (size_t)(cn + 1), hipMemcpyHostToDevice, c->stream));
-    RHIP(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipMemcpyAsync(c->d_off.p, off->data(), sizeof(int64_t) * (size_t)(cn + 1), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     *upload_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return NW_OK;
 }
@@ -618,13 +575,13 @@ int span_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, int32_t f
     sa.t = t;
     sa.slot = c->d_slot.p + r0;
     sa.ctr = c->d_ctr.p;
-    RHIP(c, hipEventRecord(c->ev[0], c->stream));
+    HIP_TRY(c, hipEventRecord(c->ev[0], c->stream));
     hipLaunchKernelGGL(nwr::nwr_span_kernel, dim3((unsigned)((sa.cn + nwr::kBlk - 1) / nwr::kBlk)), dim3(nwr::kBlk), 0, c->stream, sa);
-    RHIP(c, hipGetLastError());
-    RHIP(c, hipEventRecord(c->ev[1], c->stream));
-    RHIP(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[1], c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
     float ms = 0.0f;
-    RHIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     *kernel_ms += ms;
     return NW_OK;
 }
@@ -634,10 +591,10 @@ int emit_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, int32_t f
                std::vector<int64_t>* cursor, nwr::Hits* out, float* kernel_ms, float* upload_ms) {
     hipStream_t st = c->stream;
     const int64_t cn = r1 - r0, blocks = (cn + nwr::kBlk - 1) / nwr::kBlk;
-    RHIP(c, c->d_counts.reserve((size_t)cn));
-    RHIP(c, c->d_sums.reserve((size_t)blocks));
-    RHIP(c, c->d_totals.reserve(2));
-    RHIP(c, hipMemsetAsync(c->d_totals.p, 0, 2 * sizeof(unsigned long long), st));
+    HIP_TRY(c, c->d_counts.reserve((size_t)cn));
+    HIP_TRY(c, c->d_sums.reserve((size_t)blocks));
+    HIP_TRY(c, c->d_totals.reserve(2));
+    HIP_TRY(c, hipMemsetAsync(c->d_totals.p, 0, 2 * sizeof(unsigned long long), st));
     nwr::Args a{};
     a.cn = (int32_t)cn;
     a.flags = flags;
@@ -647,20 +604,20 @@ int emit_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, int32_t f
     a.totals = c->d_totals.p;
     a.slot = c->d_slot.p + r0;
     a.map = c->d_map.p;
-    RHIP(c, hipEventRecord(c->ev[0], st));
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
     hipLaunchKernelGGL(nwr::nwr_mark_kernel, dim3((unsigned)blocks), dim3(nwr::kBlk), 0, st, a);
-    RHIP(c, hipGetLastError());
-    RHIP(c, hipEventRecord(c->ev[1], st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[1], st));
     unsigned long long totals[2] = {0, 0};
-    RHIP(c, hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, st));
-    RHIP(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     float ms = 0.0f;
-    RHIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     *kernel_ms += ms;
     const int64_t nh = (int64_t)totals[nwr::kHits];
     if (nh > nwr::kMaxHits)
-        return rfail(c, NW_E_UNSUPPORTED, "%lld hits in the chunk of records %lld to %lld: at most 2^30 (use a smaller CRISPR_NWR_CHUNK)",
-                     (long long)nh, (long long)r0, (long long)r1);
+        return fail(c, NW_E_UNSUPPORTED, "%lld hits in the chunk of records %lld to %lld: at most 2^30 (use a smaller CRISPR_NWR_CHUNK)",
+                    (long long)nh, (long long)r0, (long long)r1);
     if (nh == 0) return NW_OK;      // (a chunk of off-target records alone is not uploaded again)
     std::vector<int64_t> off;
     const int rc = upload_chunk(c, bam, r0, r1, false, &off, resident ? nullptr : upload_ms);
@@ -679,15 +636,15 @@ int run_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, nwr::Args 
     const int64_t blocks = (cn + nwr::kBlk - 1) / nwr::kBlk;
     std::vector<int64_t> off((size_t)cn + 1);
     for (int64_t i = 0; i <= cn; ++i) off[(size_t)i] = bam->off[(size_t)(r0 + i)] - base;
-    RHIP(c, c->d_data.reserve((size_t)nbytes));
-    RHIP(c, c->d_off.reserve((size_t)cn + 1));
-    RHIP(c, c->d_counts.reserve((size_t)cn));
-    RHIP(c, c->d_sums.reserve((size_t)blocks));
+    HIP_TRY(c, c->d_data.reserve((size_t)nbytes));
+    HIP_TRY(c, c->d_off.reserve((size_t)cn + 1));
+    HIP_TRY(c, c->d_counts.reserve((size_t)cn));
+    HIP_TRY(c, c->d_sums.reserve((size_t)blocks));
     const auto t0 = std::chrono::steady_clock::now();
-    RHIP(c, hipMemcpyAsync(c->d_data.p, bam->data.data() + base, (size_t)nbytes, hipMemcpyHostToDevice, st));
-    RHIP(c, hipMemcpyAsync(c->d_off.p, off.data(), sizeof(int64_t) * (size_t)(cn + 1), hipMemcpyHostToDevice, st));
-    RHIP(c, hipMemsetAsync(c->d_totals.p, 0, 2 * sizeof(unsigned long long), st));
-    RHIP(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_data.p, bam->data.data() + base, (size_t)nbytes, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_off.p, off.data(), sizeof(int64_t) * (size_t)(cn + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->d_totals.p, 0, 2 * sizeof(unsigned long long), st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     *upload_ms += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     a.data = c->d_data.p;
     a.off = c->d_off.p;
@@ -696,21 +653,21 @@ int run_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, nwr::Args 
     a.sums = c->d_sums.p;
     a.blocks = blocks;
     a.totals = c->d_totals.p;
-    RHIP(c, hipEventRecord(c->ev[0], st));
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
     hipLaunchKernelGGL(nwr::nwr_count_kernel, dim3((unsigned)blocks), dim3(nwr::kBlk), 0, st, a);
-    RHIP(c, hipGetLastError());
-    RHIP(c, hipEventRecord(c->ev[1], st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[1], st));
     unsigned long long totals[2] = {0, 0};
-    RHIP(c, hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, st));
-    RHIP(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipMemcpyAsync(totals, a.totals, sizeof totals, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
     float ms = 0.0f;
-    RHIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
     *kernel_ms += ms;
     *n_no_seq += (int64_t)totals[nwr::kNoSeq];
     const int64_t nh = (int64_t)totals[nwr::kHits];
     if (nh > nwr::kMaxHits)
-        return rfail(c, NW_E_UNSUPPORTED, "%lld hits in the chunk of records %lld to %lld: at most 2^30 (use a smaller CRISPR_NWR_CHUNK)",
-                     (long long)nh, (long long)r0, (long long)r1);
+        return fail(c, NW_E_UNSUPPORTED, "%lld hits in the chunk of records %lld to %lld: at most 2^30 (use a smaller CRISPR_NWR_CHUNK)",
+                    (long long)nh, (long long)r0, (long long)r1);
     if (nh == 0) return NW_OK;
     return finish_chunk(c, bam, r0, r1, off, a, nh, nwr::nwr_write_kernel, false, perm, n_regions, cursor, out, kernel_ms);
 }
@@ -724,18 +681,18 @@ int finish_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, const s
     hipStream_t st = c->stream;
     const int64_t cn = r1 - r0, blocks = a.blocks;
     float ms = 0.0f;
-    RHIP(c, c->d_hits.reserve((size_t)nh));
+    HIP_TRY(c, c->d_hits.reserve((size_t)nh));
     a.hits = c->d_hits.p;
-    RHIP(c, hipEventRecord(c->ev[2], st));
+    HIP_TRY(c, hipEventRecord(c->ev[2], st));
     hipLaunchKernelGGL(nwr::nwr_scan_kernel, dim3(1), dim3(nwr::kScanBlk), 0, st, a);
-    RHIP(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
     hipLaunchKernelGGL(write_kernel, dim3((unsigned)blocks), dim3(nwr::kBlk), 0, st, a);
-    RHIP(c, hipGetLastError());
-    RHIP(c, hipEventRecord(c->ev[3], st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[3], st));
     std::vector<uint4> hits((size_t)nh);
-    RHIP(c, hipMemcpyAsync(hits.data(), a.hits, sizeof(uint4) * (size_t)nh, hipMemcpyDeviceToHost, st));
-    RHIP(c, hipStreamSynchronize(st));
-    RHIP(c, hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
+    HIP_TRY(c, hipMemcpyAsync(hits.data(), a.hits, sizeof(uint4) * (size_t)nh, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[2], c->ev[3]));
     *kernel_ms += ms;
 
     // region-major, record order within a region: a stable counting sort on the caller's region
@@ -744,7 +701,7 @@ int finish_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, const s
     std::fill(cur.begin(), cur.end(), 0);
     for (const uint4& h : hits) {
         if ((int64_t)h.x >= (by_ref ? n_regions : (int64_t)perm.size()) || (int64_t)h.y >= cn)
-            return rfail(c, NW_E_STATE, "inconsistent hit");
+            return fail(c, NW_E_STATE, "inconsistent hit");
         ++cur[(size_t)(by_ref ? (int32_t)h.x : perm[h.x]) + 1];
     }
     for (int64_t g = 0; g < n_regions; ++g) cur[(size_t)g + 1] += cur[(size_t)g];
@@ -775,29 +732,29 @@ int finish_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, const s
     for (int64_t k = 0; k < nh; ++k) out->toff[(size_t)k + 1] = out->toff[(size_t)k] + len[(size_t)k];
     const int64_t total = out->toff[(size_t)nh];
     if (total >= ((int64_t)1 << 32))
-        return rfail(c, NW_E_UNSUPPORTED, "%lld output bytes in the chunk of records %lld to %lld: under 2^32 (use a smaller CRISPR_NWR_CHUNK)",
-                     (long long)total, (long long)r0, (long long)r1);
+        return fail(c, NW_E_UNSUPPORTED, "%lld output bytes in the chunk of records %lld to %lld: under 2^32 (use a smaller CRISPR_NWR_CHUNK)",
+                    (long long)total, (long long)r0, (long long)r1);
     if (total == 0) return NW_OK;
     std::vector<uint32_t> ooff((size_t)nh + 1);
     for (int64_t k = 0; k <= nh; ++k) ooff[(size_t)k] = (uint32_t)out->toff[(size_t)k];
     const int64_t words = (total + 3) / 4;
-    RHIP(c, c->d_eh.reserve((size_t)nh));
-    RHIP(c, c->d_ooff.reserve((size_t)nh + 1));
-    RHIP(c, c->d_text.reserve((size_t)words));
-    RHIP(c, c->d_quals.reserve((size_t)words));
-    RHIP(c, hipMemcpyAsync(c->d_eh.p, eh.data(), sizeof(nwr::EmitHit) * (size_t)nh, hipMemcpyHostToDevice, st));
-    RHIP(c, hipMemcpyAsync(c->d_ooff.p, ooff.data(), sizeof(uint32_t) * (size_t)(nh + 1), hipMemcpyHostToDevice, st));
-    RHIP(c, hipEventRecord(c->ev[4], st));
+    HIP_TRY(c, c->d_eh.reserve((size_t)nh));
+    HIP_TRY(c, c->d_ooff.reserve((size_t)nh + 1));
+    HIP_TRY(c, c->d_text.reserve((size_t)words));
+    HIP_TRY(c, c->d_quals.reserve((size_t)words));
+    HIP_TRY(c, hipMemcpyAsync(c->d_eh.p, eh.data(), sizeof(nwr::EmitHit) * (size_t)nh, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_ooff.p, ooff.data(), sizeof(uint32_t) * (size_t)(nh + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipEventRecord(c->ev[4], st));
     hipLaunchKernelGGL(nwr::nwr_emit_kernel, dim3((unsigned)((words + 255) / 256)), dim3(256), 0, st, c->d_data.p, c->d_eh.p,
                        c->d_ooff.p, nh, total, c->d_text.p, c->d_quals.p);
-    RHIP(c, hipGetLastError());
-    RHIP(c, hipEventRecord(c->ev[5], st));
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[5], st));
     out->text.resize((size_t)words * 4);
     out->quals.resize((size_t)words * 4);
-    RHIP(c, hipMemcpyAsync(out->text.data(), c->d_text.p, (size_t)words * 4, hipMemcpyDeviceToHost, st));
-    RHIP(c, hipMemcpyAsync(out->quals.data(), c->d_quals.p, (size_t)words * 4, hipMemcpyDeviceToHost, st));
-    RHIP(c, hipStreamSynchronize(st));
-    RHIP(c, hipEventElapsedTime(&ms, c->ev[4], c->ev[5]));
+    HIP_TRY(c, hipMemcpyAsync(out->text.data(), c->d_text.p, (size_t)words * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(out->quals.data(), c->d_quals.p, (size_t)words * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[4], c->ev[5]));
     *kernel_ms += ms;
     out->text.resize((size_t)total);
     out->quals.resize((size_t)total);
@@ -861,70 +818,30 @@ void merge_chunks(std::vector<nwr::Hits>& chunks, int64_t n_regions, nwr::Result
 extern "C" {
 
 int nwr_create(int device, nwr_ctx** out) {
-    if (!out) return NW_E_INVALID;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return NW_E_HIP;
-    nwr_ctx* c = new nwr_ctx();
-    c->device = device;
-    bool ok = hipSetDevice(device) == hipSuccess &&
-              hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; ok && i < 6; ++i) ok = hipEventCreate(&c->ev[i]) == hipSuccess;
-    if (!ok) {
-        nwr_destroy(c);
-        return NW_E_HIP;
-    }
+    const int rc = hd::create_context(device, 6, out);
+    if (rc != NW_OK) return rc;
+    nwr_ctx* c = *out;
     if (const char* e = std::getenv("CRISPR_NWR_CHUNK"))
         c->chunk_records = std::max<int64_t>(0, std::min<int64_t>(std::atoll(e), nwr::kChunkRecords));
-    if (const char* e = std::getenv("CRISPR_NWR_HASH_BITS")) c->hash_bits = std::max(0, std::min(64, std::atoi(e)));
-    *out = c;
+    c->hash_bits = grp::env_hash_bits("CRISPR_NWR_HASH_BITS");
     return NW_OK;
 }
 
-void nwr_destroy(nwr_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    c->d_data.release();
-    c->d_off.release();
-    c->d_rstart.release();
-    c->d_rend.release();
-    c->d_rref.release();
-    c->d_counts.release();
-    c->d_sums.release();
-    c->d_ooff.release();
-    c->d_text.release();
-    c->d_quals.release();
-    c->d_totals.release();
-    c->d_hits.release();
-    c->d_eh.release();
-    c->d_w0.release();
-    c->d_w1.release();
-    c->d_ctr.release();
-    c->d_tcount.release();
-    c->d_slot.release();
-    c->d_lslot.release();
-    c->d_map.release();
-    c->d_lreg.release();
-    c->d_list.release();
-    for (hipEvent_t e : c->ev)
-        if (e) (void)hipEventDestroy(e);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
-    delete c;
-}
+void nwr_destroy(nwr_ctx* c) { hd::destroy_context(c); }
 
 const char* nwr_last_error(const nwr_ctx* c) { return c ? c->err.c_str() : "null context"; }
 
 int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64_t n_regions, int32_t flags,
                 nwr_result* res) {
     if (!c) return NW_E_INVALID;
-    if (!bam || !res) return rfail(c, NW_E_INVALID, "null argument");
+    if (!bam || !res) return fail(c, NW_E_INVALID, "null argument");
     std::memset(res, 0, sizeof *res);
-    if (flags & ~(NWR_BY_REFERENCE | NWR_EQX_AS_MATCH)) return rfail(c, NW_E_INVALID, "unknown flags %d", (int)flags);
+    if (flags & ~(NWR_BY_REFERENCE | NWR_EQX_AS_MATCH)) return fail(c, NW_E_INVALID, "unknown flags %d", (int)flags);
     const bool by_ref = (flags & NWR_BY_REFERENCE) != 0;
     if (by_ref) n_regions = (int64_t)bam->ref_len.size();
-    if (n_regions < 0 || (!by_ref && n_regions > 0 && !regions)) return rfail(c, NW_E_INVALID, "null regions");
+    if (n_regions < 0 || (!by_ref && n_regions > 0 && !regions)) return fail(c, NW_E_INVALID, "null regions");
     if (n_regions > NWR_MAX_REGIONS)
-        return rfail(c, NW_E_UNSUPPORTED, "%lld regions: at most %d are supported", (long long)n_regions, NWR_MAX_REGIONS);
+        return fail(c, NW_E_UNSUPPORTED, "%lld regions: at most %d are supported", (long long)n_regions, NWR_MAX_REGIONS);
     const int64_t n = (int64_t)bam->off.size() - 1;
     nwr::Result* R = new nwr::Result();
     R->region_off.assign((size_t)n_regions + 1, 0);
@@ -940,9 +857,9 @@ int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64
     nwr::Args a{};
     a.flags = flags;
     std::vector<int32_t> perm;
-    if (hipSetDevice(c->device) != hipSuccess) return bail(rfail(c, NW_E_HIP, "hipSetDevice failed"));
+    if (hipSetDevice(c->device) != hipSuccess) return bail(fail(c, NW_E_HIP, "hipSetDevice failed"));
     int rc = [&]() -> int {
-        RHIP(c, c->d_totals.reserve(2));
+        HIP_TRY(c, c->d_totals.reserve(2));
         if (by_ref) return NW_OK;
         // the table in (ref, bpstart) order, equal keys in the caller's order; perm leads back
         perm.resize((size_t)n_regions);
@@ -959,12 +876,12 @@ int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64
             rstart[(size_t)g] = r.bpstart;
             rend[(size_t)g] = r.bpend;
         }
-        RHIP(c, c->d_rref.reserve((size_t)n_regions));
-        RHIP(c, c->d_rstart.reserve((size_t)n_regions));
-        RHIP(c, c->d_rend.reserve((size_t)n_regions));
-        RHIP(c, hipMemcpy(c->d_rref.p, rref.data(), sizeof(int32_t) * (size_t)n_regions, hipMemcpyHostToDevice));
-        RHIP(c, hipMemcpy(c->d_rstart.p, rstart.data(), sizeof(int64_t) * (size_t)n_regions, hipMemcpyHostToDevice));
-        RHIP(c, hipMemcpy(c->d_rend.p, rend.data(), sizeof(int64_t) * (size_t)n_regions, hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_rref.reserve((size_t)n_regions));
+        HIP_TRY(c, c->d_rstart.reserve((size_t)n_regions));
+        HIP_TRY(c, c->d_rend.reserve((size_t)n_regions));
+        HIP_TRY(c, hipMemcpy(c->d_rref.p, rref.data(), sizeof(int32_t) * (size_t)n_regions, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_rstart.p, rstart.data(), sizeof(int64_t) * (size_t)n_regions, hipMemcpyHostToDevice));
+        HIP_TRY(c, hipMemcpy(c->d_rend.p, rend.data(), sizeof(int64_t) * (size_t)n_regions, hipMemcpyHostToDevice));
         a.nreg = (int32_t)n_regions;
         a.rref = c->d_rref.p;
         a.rstart = c->d_rstart.p;
@@ -991,12 +908,12 @@ int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64
 
 int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_reads, nwr_result* res) {
     if (!c) return NW_E_INVALID;
-    if (!bam || !res) return rfail(c, NW_E_INVALID, "null argument");
+    if (!bam || !res) return fail(c, NW_E_INVALID, "null argument");
     std::memset(res, 0, sizeof *res);
-    if (flags & ~NWR_EQX_AS_MATCH) return rfail(c, NW_E_INVALID, "unknown flags %d", (int)flags);
+    if (flags & ~NWR_EQX_AS_MATCH) return fail(c, NW_E_INVALID, "unknown flags %d", (int)flags);
     const int64_t n = (int64_t)bam->off.size() - 1;
     if (n > ((int64_t)1 << 30))
-        return rfail(c, NW_E_UNSUPPORTED, "%lld records: at most 2^30 in one nwr_discover call", (long long)n);
+        return fail(c, NW_E_UNSUPPORTED, "%lld records: at most 2^30 in one nwr_discover call", (long long)n);
     nwr::Result* R = new nwr::Result();
     R->discovered = true;
     R->region_off.assign(1, 0);
@@ -1005,7 +922,7 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
     if (hipSetDevice(c->device) != hipSuccess) {
         delete R;
         res->handle = nullptr;
-        return rfail(c, NW_E_HIP, "hipSetDevice failed");
+        return fail(c, NW_E_HIP, "hipSetDevice failed");
     }
 
     std::vector<nwr::Hits> chunks;
@@ -1013,25 +930,24 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
     const int rc = [&]() -> int {
         hipStream_t st = c->stream;
         // the table: a power of two of at least twice the records, so the load stays <= 1/2
-        int log2 = 10;
-        while (((int64_t)1 << log2) < 2 * n) ++log2;
-        const size_t slots = (size_t)1 << log2;
-        RHIP(c, c->d_w0.reserve(slots));
-        RHIP(c, c->d_w1.reserve(slots));
-        RHIP(c, c->d_tcount.reserve(slots));
-        RHIP(c, c->d_slot.reserve((size_t)n));
-        RHIP(c, c->d_ctr.reserve(nwr::kCounters));
-        RHIP(c, hipMemsetAsync(c->d_w0.p, 0, sizeof(unsigned long long) * slots, st));
-        RHIP(c, hipMemsetAsync(c->d_w1.p, 0, sizeof(unsigned long long) * slots, st));
-        RHIP(c, hipMemsetAsync(c->d_tcount.p, 0, sizeof(uint32_t) * slots, st));
-        RHIP(c, hipMemsetAsync(c->d_ctr.p, 0, sizeof(unsigned long long) * nwr::kCounters, st));
+        const grp::TableGeometry tg = grp::table_geometry(n, c->hash_bits);
+        const size_t slots = tg.slots;
+        HIP_TRY(c, c->d_w0.reserve(slots));
+        HIP_TRY(c, c->d_w1.reserve(slots));
+        HIP_TRY(c, c->d_tcount.reserve(slots));
+        HIP_TRY(c, c->d_slot.reserve((size_t)n));
+        HIP_TRY(c, c->d_ctr.reserve(nwr::kCounters));
+        HIP_TRY(c, hipMemsetAsync(c->d_w0.p, 0, sizeof(unsigned long long) * slots, st));
+        HIP_TRY(c, hipMemsetAsync(c->d_w1.p, 0, sizeof(unsigned long long) * slots, st));
+        HIP_TRY(c, hipMemsetAsync(c->d_tcount.p, 0, sizeof(uint32_t) * slots, st));
+        HIP_TRY(c, hipMemsetAsync(c->d_ctr.p, 0, sizeof(unsigned long long) * nwr::kCounters, st));
         nwr::Table t{};
         t.w0 = c->d_w0.p;
         t.w1 = c->d_w1.p;
         t.count = c->d_tcount.p;
-        t.cap_mask = (uint64_t)slots - 1;
-        t.shift = 64 - log2;
-        t.hash_mask = c->hash_bits >= 64 ? ~0ull : (((uint64_t)1 << c->hash_bits) - 1);
+        t.cap_mask = tg.cap_mask;
+        t.shift = tg.shift;
+        t.hash_mask = tg.hash_mask;
 
         std::vector<std::pair<int64_t, int64_t>> ranges;
         for (int64_t r0 = 0; r0 < n; r0 = ranges.back().second) ranges.emplace_back(r0, chunk_end(c, bam, r0, n));
@@ -1040,11 +956,11 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
             if (rc1 != NW_OK) return rc1;
         }
         unsigned long long ctr[nwr::kCounters];
-        RHIP(c, hipMemcpy(ctr, c->d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
+        HIP_TRY(c, hipMemcpy(ctr, c->d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost));
         if (ctr[nwr::kError])
-            return rfail(c, NW_E_STATE, "the span table's probe bound was reached (%zu slots, %lld records)", slots, (long long)n);
+            return fail(c, NW_E_STATE, "the span table's probe bound was reached (%zu slots, %lld records)", slots, (long long)n);
         const int64_t nd = (int64_t)ctr[nwr::kDistinct];
-        if (nd < 0 || nd > n || (int64_t)ctr[nwr::kKept] > n) return rfail(c, NW_E_STATE, "inconsistent counters");
+        if (nd < 0 || nd > n || (int64_t)ctr[nwr::kKept] > n) return fail(c, NW_E_STATE, "inconsistent counters");
         res->n_no_seq = (int64_t)ctr[nwr::kDropped];
         R->stats[0] = (int64_t)ctr[nwr::kAligned];
         R->stats[1] = (int64_t)ctr[nwr::kKept];
@@ -1052,27 +968,27 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
 
         // the used slots to the host; the regions in key order
         std::vector<nwr::Listed> list((size_t)nd);
-        RHIP(c, c->d_list.reserve((size_t)nd));
-        RHIP(c, hipEventRecord(c->ev[0], st));
+        HIP_TRY(c, c->d_list.reserve((size_t)nd));
+        HIP_TRY(c, hipEventRecord(c->ev[0], st));
         hipLaunchKernelGGL(nwr::nwr_compact_kernel, dim3((unsigned)((slots + nwr::kBlk - 1) / nwr::kBlk)), dim3(nwr::kBlk), 0, st, t,
                            c->d_list.p, (uint64_t)nd, c->d_ctr.p);
-        RHIP(c, hipGetLastError());
-        RHIP(c, hipEventRecord(c->ev[1], st));
-        RHIP(c, hipMemcpyAsync(list.data(), c->d_list.p, sizeof(nwr::Listed) * (size_t)nd, hipMemcpyDeviceToHost, st));
-        RHIP(c, hipMemcpyAsync(ctr, c->d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
-        RHIP(c, hipStreamSynchronize(st));
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->ev[1], st));
+        HIP_TRY(c, hipMemcpyAsync(list.data(), c->d_list.p, sizeof(nwr::Listed) * (size_t)nd, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(ctr, c->d_ctr.p, sizeof ctr, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
         float ms = 0.0f;
-        RHIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
         res->kernel_ms += ms;
-        if ((int64_t)ctr[nwr::kListed] != nd) return rfail(c, NW_E_STATE, "inconsistent table");
+        if ((int64_t)ctr[nwr::kListed] != nd) return fail(c, NW_E_STATE, "inconsistent table");
         std::vector<nwr_region> key((size_t)nd);
         int64_t sum = 0;
         for (int64_t e = 0; e < nd; ++e) {
             nwr::unpack_key(list[(size_t)e].w0, list[(size_t)e].w1, &key[(size_t)e]);
             sum += list[(size_t)e].count;
-            if ((uint64_t)list[(size_t)e].slot > t.cap_mask) return rfail(c, NW_E_STATE, "inconsistent table");
+            if ((uint64_t)list[(size_t)e].slot > t.cap_mask) return fail(c, NW_E_STATE, "inconsistent table");
         }
-        if (sum != R->stats[1]) return rfail(c, NW_E_STATE, "inconsistent table");
+        if (sum != R->stats[1]) return fail(c, NW_E_STATE, "inconsistent table");
         std::vector<int64_t> order((size_t)nd);
         std::iota(order.begin(), order.end(), 0);
         std::sort(order.begin(), order.end(), [&](int64_t x, int64_t y) {      // (the keys are distinct)
@@ -1081,7 +997,7 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
             if (p.bpstart != q.bpstart) return p.bpstart < q.bpstart;
             return p.bpend < q.bpend;
         });
-        if (nd > 0x7FFFFFFF) return rfail(c, NW_E_UNSUPPORTED, "%lld regions", (long long)nd);
+        if (nd > 0x7FFFFFFF) return fail(c, NW_E_UNSUPPORTED, "%lld regions", (long long)nd);
         n_regions = nd;
         R->regions.resize((size_t)nd);
         R->n_records.resize((size_t)nd);
@@ -1099,21 +1015,21 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
         }
         R->stats[2] = emitted;
         if (emitted > NWR_MAX_REGIONS)
-            return rfail(c, NW_E_UNSUPPORTED, "%lld regions to emit: at most %d are supported (raise min_reads)",
-                         (long long)emitted, NWR_MAX_REGIONS);
+            return fail(c, NW_E_UNSUPPORTED, "%lld regions to emit: at most %d are supported (raise min_reads)",
+                        (long long)emitted, NWR_MAX_REGIONS);
         if (emitted == 0) return NW_OK;
-        RHIP(c, c->d_lslot.reserve((size_t)nd));
-        RHIP(c, c->d_lreg.reserve((size_t)nd));
-        RHIP(c, c->d_map.reserve(slots));
-        RHIP(c, hipMemcpyAsync(c->d_lslot.p, lslot.data(), sizeof(uint32_t) * (size_t)nd, hipMemcpyHostToDevice, st));
-        RHIP(c, hipMemcpyAsync(c->d_lreg.p, lreg.data(), sizeof(int32_t) * (size_t)nd, hipMemcpyHostToDevice, st));
-        RHIP(c, hipEventRecord(c->ev[0], st));
+        HIP_TRY(c, c->d_lslot.reserve((size_t)nd));
+        HIP_TRY(c, c->d_lreg.reserve((size_t)nd));
+        HIP_TRY(c, c->d_map.reserve(slots));
+        HIP_TRY(c, hipMemcpyAsync(c->d_lslot.p, lslot.data(), sizeof(uint32_t) * (size_t)nd, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->d_lreg.p, lreg.data(), sizeof(int32_t) * (size_t)nd, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipEventRecord(c->ev[0], st));
         hipLaunchKernelGGL(nwr::nwr_scatter_kernel, dim3((unsigned)((nd + nwr::kBlk - 1) / nwr::kBlk)), dim3(nwr::kBlk), 0, st,
                            c->d_lslot.p, c->d_lreg.p, nd, t.cap_mask, c->d_map.p);
-        RHIP(c, hipGetLastError());
-        RHIP(c, hipEventRecord(c->ev[1], st));
-        RHIP(c, hipStreamSynchronize(st));
-        RHIP(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->ev[1], st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
         res->kernel_ms += ms;
 
         // pass 2: a one-chunk call still has its records in d_data

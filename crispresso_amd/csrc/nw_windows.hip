@@ -153,25 +153,9 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const uint32_t* rec,
     out[i] = rec[(int64_t)first[g] * s4 + (i - g * s4)];
 }
 
-void windows_release(nwa_ctx* c) {
-    c->w_rec.release();
-    c->w_amp.release();
-    c->w_unmod.release();
-    c->w_gwin.release();
-    c->w_gun.release();
-    c->w_off.release();
-    c->w_err.release();
-    c->w_gfirst.release();
-    for (hipEvent_t& e : c->wev) {
-        if (e) (void)hipEventDestroy(e);
-        e = nullptr;
-    }
-    c->w_tab.clear();
-}
-
 }  // namespace nwa
 
-using nwa::afail;
+using hd::fail;
 
 extern "C" {
 
@@ -185,23 +169,23 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
     c->w_cuts = 0;
     c->w_collided = 0;
     std::fill(c->w_ms, c->w_ms + 3, 0.0f);
-    if (n < 0 || n > 0x7FFFFFFFll) return afail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
+    if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
     if (n_cuts < 0 || (n_cuts > 0 && (!cut_points || !n_groups)) || !n_no_cut || !first_no_cut || !amplicon ||
         amp_len <= 0 || awidth <= 0)
-        return afail(c, NW_E_INVALID, "null or empty argument");
+        return fail(c, NW_E_INVALID, "null or empty argument");
     if (n > 0 && (!d_ops_off || !d_stats || !d_reads || !d_offsets || !read_results))
-        return afail(c, NW_E_INVALID, "null batch array");
+        return fail(c, NW_E_INVALID, "null batch array");
     if (offset < 1 || offset > nwa::kWinMaxOffset)
-        return afail(c, NW_E_UNSUPPORTED, "offset %d outside 1..%d", (int)offset, nwa::kWinMaxOffset);
+        return fail(c, NW_E_UNSUPPORTED, "offset %d outside 1..%d", (int)offset, nwa::kWinMaxOffset);
     if (amp_len > nwa::kWinMaxAmp)
-        return afail(c, NW_E_UNSUPPORTED, "amplicon of %d bases (at most %d)", (int)amp_len, nwa::kWinMaxAmp);
+        return fail(c, NW_E_UNSUPPORTED, "amplicon of %d bases (at most %d)", (int)amp_len, nwa::kWinMaxAmp);
     for (int32_t i = 0; i < amp_len; ++i)
         if (!std::strchr("ACGTN", amplicon[i]) || amplicon[i] == 0)
-            return afail(c, NW_E_UNSUPPORTED, "amplicon byte %d at %d is not one of ACGTN", (int)(unsigned char)amplicon[i],
-                         (int)i);
+            return fail(c, NW_E_UNSUPPORTED, "amplicon byte %d at %d is not one of ACGTN", (int)(unsigned char)amplicon[i],
+                        (int)i);
     for (int32_t k = 0; k < n_cuts; ++k)
         if (cut_points[k] < 0 || cut_points[k] >= amp_len)
-            return afail(c, NW_E_UNSUPPORTED, "cut point %d outside the amplicon", (int)cut_points[k]);
+            return fail(c, NW_E_UNSUPPORTED, "cut point %d outside the amplicon", (int)cut_points[k]);
     *n_no_cut = 0;
     *first_no_cut = -1;
     c->w_width = 2 * offset;
@@ -217,30 +201,29 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
         for (auto& t : c->w_tab) t.gor.assign((size_t)n, -1);
     if (kept == 0 || n_cuts == 0) return NW_OK;
 
-    AHIP(c, hipSetDevice(c->device));
-    for (hipEvent_t& e : c->wev)
-        if (!e) AHIP(c, hipEventCreate(&e));
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipEvent_t* const wev = &c->ev[5];
     const int W = 2 * offset, stride = 4 + 2 * W, s4 = stride / 4;
     const int Kmax = std::min<int>(nwa::kWinCuts, n_cuts);
-    AHIP(c, c->w_rec.reserve((size_t)Kmax * (size_t)n * (size_t)stride));
-    AHIP(c, c->w_amp.reserve((size_t)amp_len));
-    AHIP(c, c->w_unmod.reserve((size_t)n));
-    AHIP(c, c->w_off.reserve((size_t)n + 1));
-    AHIP(c, c->w_err.reserve(2));
-    AHIP(c, c->w_gfirst.reserve((size_t)kept));
-    AHIP(c, c->w_gun.reserve((size_t)kept));
+    HIP_TRY(c, c->w_rec.reserve((size_t)Kmax * (size_t)n * (size_t)stride));
+    HIP_TRY(c, c->w_amp.reserve((size_t)amp_len));
+    HIP_TRY(c, c->w_unmod.reserve((size_t)n));
+    HIP_TRY(c, c->w_off.reserve((size_t)n + 1));
+    HIP_TRY(c, c->w_err.reserve(2));
+    HIP_TRY(c, c->w_gfirst.reserve((size_t)kept));
+    HIP_TRY(c, c->w_gun.reserve((size_t)kept));
     if (keep) {
-        AHIP(c, c->d_keep.reserve((size_t)n));
-        AHIP(c, hipMemcpy(c->d_keep.p, keep, (size_t)n, hipMemcpyHostToDevice));
+        HIP_TRY(c, c->d_keep.reserve((size_t)n));
+        HIP_TRY(c, hipMemcpy(c->d_keep.p, keep, (size_t)n, hipMemcpyHostToDevice));
     }
     std::vector<uint8_t> unmod((size_t)n);
     for (int64_t r = 0; r < n; ++r) unmod[(size_t)r] = read_results[4 * r] == 0;
-    AHIP(c, hipMemcpy(c->w_unmod.p, unmod.data(), (size_t)n, hipMemcpyHostToDevice));
-    AHIP(c, hipMemcpy(c->w_amp.p, amplicon, (size_t)amp_len, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->w_unmod.p, unmod.data(), (size_t)n, hipMemcpyHostToDevice));
+    HIP_TRY(c, hipMemcpy(c->w_amp.p, amplicon, (size_t)amp_len, hipMemcpyHostToDevice));
     hipStream_t st = c->stream;
     hipLaunchKernelGGL(nwa::window_offsets_kernel, dim3((unsigned)(n / 256 + 1)), dim3(256), 0, st, c->w_off.p, n,
                        (int64_t)stride);
-    AHIP(c, hipGetLastError());
+    HIP_TRY(c, hipGetLastError());
 
     std::vector<int64_t> first((size_t)kept), count((size_t)kept);
     std::vector<int32_t> gor((size_t)n);
@@ -267,18 +250,18 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
         a.rec = c->w_rec.p;
         a.err = c->w_err.p;
         const uint32_t err0[2] = {0u, 0xFFFFFFFFu};
-        AHIP(c, hipMemcpyAsync(c->w_err.p, err0, sizeof err0, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->w_err.p, err0, sizeof err0, hipMemcpyHostToDevice, st));
         const int64_t blocks = (n * K + nwa::kWinBlock - 1) / nwa::kWinBlock;
         const size_t lds = sizeof(uint32_t) * ((size_t)((amp_len + 3) >> 2) + (size_t)nwa::kWinBlock * s4);
-        AHIP(c, hipEventRecord(c->wev[0], st));
+        HIP_TRY(c, hipEventRecord(wev[0], st));
         hipLaunchKernelGGL(nwa::window_extract_kernel, dim3((unsigned)blocks), dim3(nwa::kWinBlock), lds, st, a);
-        AHIP(c, hipGetLastError());
-        AHIP(c, hipEventRecord(c->wev[1], st));
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(wev[1], st));
         uint32_t err[2] = {0, 0};
-        AHIP(c, hipMemcpyAsync(err, c->w_err.p, sizeof err, hipMemcpyDeviceToHost, st));
-        AHIP(c, hipStreamSynchronize(st));
+        HIP_TRY(c, hipMemcpyAsync(err, c->w_err.p, sizeof err, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
         float ms = 0;
-        AHIP(c, hipEventElapsedTime(&ms, c->wev[0], c->wev[1]));
+        HIP_TRY(c, hipEventElapsedTime(&ms, wev[0], wev[1]));
         c->w_ms[0] += ms;
         if (err[0]) {                 // the reference's ValueError: the caller raises, nothing is kept
             *n_no_cut = err[0];
@@ -295,32 +278,32 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
             const int rc = nwa_group_device(c, rec_k, c->w_off.p, 0, n, keep, tag, first.data(), count.data(), kept,
                                             gor.data(), &ng, &ms);
             if (rc != NW_OK) return rc;
-            if (ng <= 0 || ng > kept) return afail(c, NW_E_STATE, "inconsistent window group count");
+            if (ng <= 0 || ng > kept) return fail(c, NW_E_STATE, "inconsistent window group count");
             c->w_ms[1] += ms;
             c->w_collided += c->collided;
             // collided records were regrouped on the host: the device copy of group_of_read follows
             if (c->collided)
-                AHIP(c, hipMemcpyAsync(c->d_gor.p, gor.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
+                HIP_TRY(c, hipMemcpyAsync(c->d_gor.p, gor.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice, st));
             first32.resize((size_t)ng);
             for (int64_t g = 0; g < ng; ++g) first32[(size_t)g] = (uint32_t)first[(size_t)g];
-            AHIP(c, c->w_gwin.reserve((size_t)ng * (size_t)stride));
-            AHIP(c, hipMemcpyAsync(c->w_gfirst.p, first32.data(), sizeof(uint32_t) * (size_t)ng, hipMemcpyHostToDevice, st));
-            AHIP(c, hipMemsetAsync(c->w_gun.p, 0, (size_t)ng, st));
-            AHIP(c, hipEventRecord(c->wev[0], st));
+            HIP_TRY(c, c->w_gwin.reserve((size_t)ng * (size_t)stride));
+            HIP_TRY(c, hipMemcpyAsync(c->w_gfirst.p, first32.data(), sizeof(uint32_t) * (size_t)ng, hipMemcpyHostToDevice, st));
+            HIP_TRY(c, hipMemsetAsync(c->w_gun.p, 0, (size_t)ng, st));
+            HIP_TRY(c, hipEventRecord(wev[0], st));
             hipLaunchKernelGGL(nwa::window_unedited_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st,
                                c->d_gor.p, c->w_unmod.p, n, c->w_gun.p);
-            AHIP(c, hipGetLastError());
+            HIP_TRY(c, hipGetLastError());
             hipLaunchKernelGGL(nwa::window_gather_kernel, dim3((unsigned)((ng * s4 + 255) / 256)), dim3(256), 0, st,
                                reinterpret_cast<const uint32_t*>(rec_k), c->w_gfirst.p, ng, s4,
                                reinterpret_cast<uint32_t*>(c->w_gwin.p));
-            AHIP(c, hipGetLastError());
-            AHIP(c, hipEventRecord(c->wev[1], st));
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipEventRecord(wev[1], st));
             t.unedited.resize((size_t)ng);
             recs.resize((size_t)ng * (size_t)s4);
-            AHIP(c, hipMemcpyAsync(t.unedited.data(), c->w_gun.p, (size_t)ng, hipMemcpyDeviceToHost, st));
-            AHIP(c, hipMemcpyAsync(recs.data(), c->w_gwin.p, (size_t)ng * (size_t)stride, hipMemcpyDeviceToHost, st));
-            AHIP(c, hipStreamSynchronize(st));
-            AHIP(c, hipEventElapsedTime(&ms, c->wev[0], c->wev[1]));
+            HIP_TRY(c, hipMemcpyAsync(t.unedited.data(), c->w_gun.p, (size_t)ng, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipMemcpyAsync(recs.data(), c->w_gwin.p, (size_t)ng * (size_t)stride, hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipStreamSynchronize(st));
+            HIP_TRY(c, hipEventElapsedTime(&ms, wev[0], wev[1]));
             c->w_ms[2] += ms;
             t.first.assign(first.begin(), first.begin() + ng);
             t.count.assign(count.begin(), count.begin() + ng);

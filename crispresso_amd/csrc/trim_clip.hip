@@ -453,7 +453,7 @@ bool run_clip(Batch& b, const nwt_params* params, const Tables* d_t, int lmax, i
     a.pal_thr = (float)params->palindrome_threshold;
     a.simple_thr = (float)params->simple_threshold;
     a.log10_4 = log10_4;
-    if (hipEventRecord(b.e0, nullptr) != hipSuccess) return false;
+    if (!b.begin()) return false;
     hipLaunchKernelGGL(nwt_clip_kernel, dim3(b.grid(n, a.wpb)), dim3(64 * a.wpb), lds, nullptr, a);
     return b.elapsed(ms);
 }
@@ -517,7 +517,7 @@ bool program_run(Batch& b, Program& P, int lmax, int64_t n, bool paired, int32_t
     const size_t lds_wave = steps_lds_per_wave(lmax, &sa.lb);
     // 1 wave: reads in the thousands of bases (<= 21 KB a wave)
     sa.wpb = lds_wave * kWpb <= 65536 ? kWpb : 1;
-    if (hipEventRecord(b.e0, nullptr) != hipSuccess) return false;
+    if (!b.begin()) return false;
     launch_steps(sa, b.grid(paired ? 2 * n : n, sa.wpb), lds_wave * sa.wpb);
     return b.elapsed(kernel_ms ? kernel_ms + 1 : nullptr);
 }

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "../../include/crispr_trim.h"
+#include "host_dev.h"
 
 namespace nwt {
 
@@ -36,26 +37,13 @@ size_t steps_lds_per_wave(int lmax, int32_t* lb);
 // Launches nwt_steps_kernel on the null stream (a.wpb waves per block, `grid` blocks).
 void launch_steps(const StepsArgs& a, unsigned grid, size_t lds);
 
-// The device side of one call: the uploaded reads, the output arrays, two events.  Everything
-// is released when it goes out of scope.
-struct Batch {
-    std::vector<void*> bufs;
+// The device side of one call: the bag of its allocations and events, the uploaded reads and
+// the launch cap.
+struct Batch : hd::DevBag {
     uint8_t *s1 = nullptr, *q1 = nullptr, *s2 = nullptr, *q2 = nullptr;
     int64_t *o1 = nullptr, *o2 = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
     int cus = 256;
 
-    ~Batch() {
-        if (e0) (void)hipEventDestroy(e0);
-        if (e1) (void)hipEventDestroy(e1);
-        for (void* p : bufs) (void)hipFree(p);
-    }
-    void* dev(size_t bytes) {
-        void* p = nullptr;
-        if (hipMalloc(&p, std::max<size_t>(bytes, 16)) != hipSuccess) return nullptr;
-        bufs.push_back(p);
-        return p;
-    }
     // allocates the read buffers (the caller allocates its own before upload() and checks them all there)
     bool alloc_reads(int64_t t1, int64_t t2, int64_t n) {
         s1 = (uint8_t*)dev(t1 + 8);
@@ -76,24 +64,18 @@ struct Batch {
             ok = hipMemcpy(s2, seq2, t2, hipMemcpyHostToDevice) == hipSuccess &&
                  hipMemcpy(q2, qual2, t2, hipMemcpyHostToDevice) == hipSuccess &&
                  hipMemcpy(o2, off2, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice) == hipSuccess;
-        return ok && begin(device);
-    }
-    // the events and the launch cap: what a call needs once its reads are on the device
-    bool begin(int device) {
-        const bool ok = hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess;
-        hipDeviceProp_t prop;
-        if (ok && hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
-            cus = prop.multiProcessorCount;
+        set_launch_cap(device);
         return ok;
+    }
+    // the launch cap: what a call needs once its reads are on the device
+    void set_launch_cap(int device) {
+        hipDeviceProp_t prop;
+        if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
+            cus = prop.multiProcessorCount;
     }
     // blocks for `items` wavefront jobs at wpb a block: the launch cap both kernels share
     unsigned grid(int64_t items, int wpb) const {
         return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + wpb - 1) / wpb, (int64_t)cus * 16));
-    }
-    // what ran between record(e0) and here, in ms
-    bool elapsed(float* ms) {
-        return hipGetLastError() == hipSuccess && hipEventRecord(e1, nullptr) == hipSuccess &&
-               hipEventSynchronize(e1) == hipSuccess && (!ms || hipEventElapsedTime(ms, e0, e1) == hipSuccess);
     }
 };
 
