@@ -70,6 +70,13 @@ COUNT_EXPORTS = (
     "nwc_phase_times",
 )
 
+# Every symbol include/crispr_demux.h declares.
+DEMUX_EXPORTS = (
+    "nwd_create", "nwd_destroy", "nwd_last_error", "nwd_set_amplicons", "nwd_assign", "nwd_gather",
+    "nwd_last_fallback", "nwd_phase_times",
+)
+NWD_NO_HIT, NWD_TIE = -1, -2
+
 # Every symbol include/crispr_regions.h declares.
 REGION_EXPORTS = (
     "nwr_read_bam", "nwr_bam_free", "nwr_bam_count", "nwr_bam_data", "nwr_bam_offsets", "nwr_bam_n_ref",
@@ -325,6 +332,15 @@ def load() -> ctypes.CDLL:
         "nwc_fetch_groups": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64]),
         "nwc_last_collided": (c_int64, [ctx_p]),
         "nwc_phase_times": (c_int, [ctx_p, c_void_p]),
+        "nwd_create": (c_int, [c_int, POINTER(c_void_p)]),
+        "nwd_destroy": (None, [ctx_p]),
+        "nwd_last_error": (c_char_p, [ctx_p]),
+        "nwd_set_amplicons": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_int32, POINTER(c_int64), POINTER(c_int64)]),
+        "nwd_assign": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p] + [POINTER(c_int64)] * 3 + [POINTER(c_float)]),
+        "nwd_gather": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
+        "nwd_last_fallback": (c_int64, [ctx_p]),
+        "nwd_phase_times": (c_int, [ctx_p, c_void_p]),
         "nwr_read_bam": (c_int, [c_char_p, c_void_p, c_int64, POINTER(c_void_p), c_char_p, c_int64]),
         "nwr_bam_free": (None, [c_void_p]),
         "nwr_bam_count": (c_int64, [c_void_p]),
@@ -384,7 +400,7 @@ def exported_symbols() -> dict:
     """Map of each declared symbol to whether the loaded library exports it."""
     lib = load()
     out = {}
-    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + COUNT_EXPORTS + REGION_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + INGEST_EXPORTS + SYNTH_EXPORTS:
+    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + COUNT_EXPORTS + DEMUX_EXPORTS + REGION_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + INGEST_EXPORTS + SYNTH_EXPORTS:
         try:
             getattr(lib, name)
             out[name] = name not in _MISSING

@@ -1,0 +1,113 @@
+/* crispr_demux.h -- C ABI of the MI355X pooled-amplicon demultiplexing.
+ *
+ * Replaces the bowtie2 step of CRISPRessoPooled's ONLY_AMPLICONS mode
+ * (CRISPResso/CRISPRessoPooledCORE.py:843-878): the index of the amplicons, the mapping of every
+ * read, and the split of the mapped reads into one set per amplicon.  It is not bowtie2 (no seed
+ * extension, no random tie-break, no MAPQ, no soft clipping, no genome); it is the rule below,
+ * deterministic, restated in tests/demux_model.py.
+ *
+ * Parameters: k, the window length, 8 <= k <= 31 (a window is an exact 2k-bit key); min_hits >= 1;
+ * both_strands.
+ *
+ * Bases: A C G T a c g t map to 0..3 (case is ignored, as in the packer).  Any other byte is a
+ * break: a window that contains a break casts no vote, in an amplicon or in a read.
+ *
+ * Index: every break-free length-k window of every amplicon's forward strand maps to that
+ * amplicon's index g.  A window that occurs in two or more distinct amplicons maps to AMBIGUOUS
+ * and never votes; repeats inside one amplicon stay g.  The index is a function of the amplicon
+ * set alone (insertion order does not show in it).
+ *
+ * Votes, for a read of n bytes and every p in [0, n - k]: if w = read[p .. p + k) is break-free
+ * and indexed to g, it is one vote for (g, strand 0); with both_strands, if the reverse
+ * complement of w is indexed to g', it is one vote for (g', strand 1).  A palindromic window
+ * votes on both strands.
+ *
+ * Decision: best = the largest vote count over all (g, s) pairs; rival = the largest count over
+ * all other pairs (the same amplicon on the other strand is a rival);
+ *   which = g, strand = s   iff best >= min_hits and best > rival;
+ *   which = NWD_NO_HIT      when best < min_hits (reads shorter than k, the empty read);
+ *   which = NWD_TIE         otherwise.
+ * votes (= best) and rival are returned per read for all three outcomes; strand is 0 for a read
+ * that is not assigned.
+ *
+ * Gathered output: group g holds the reads with which == g in ascending input index.  A strand-1
+ * read's bytes are reversed and complemented (A<->T C<->G a<->t c<->g, every other byte
+ * unchanged): what bowtie2's SAM field 10 would hold, the amplicon's orientation.  Strand-0 reads
+ * are copied as given.
+ *
+ * The result is a function of the input alone (no atomic ordering shows in it).  The binding is
+ * crispresso_amd/demux.py (ctypes).  Error codes are the NW_E_* of include/crispr_nw.h.
+ */
+#ifndef CRISPR_DEMUX_H
+#define CRISPR_DEMUX_H
+
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+typedef struct nwd_ctx nwd_ctx;
+
+#define NWD_NO_HIT (-1)
+#define NWD_TIE (-2)
+#define NWD_MIN_K 8
+#define NWD_MAX_K 31
+#define NWD_MAX_REFS 65535
+#define NWD_MAX_REF_BASES (1 << 24)
+#define NWD_MAX_READ 4096
+#define NWD_MAX_TALLY_SLOTS 256
+
+/* Read here, so that tests reach the edges on small inputs:
+ *   CRISPR_NWD_CHUNK=<reads>       reads per chunk (default: chunks of about 64 MiB of text);
+ *   CRISPR_NWD_TALLY_SLOTS=<s>     (1..NWD_MAX_TALLY_SLOTS, default 64) distinct (amplicon, strand)
+ *                                  candidates a read's tally holds on the device; a read with
+ *                                  more is decided by the exact path (nwd_last_fallback). */
+int nwd_create(int device, nwd_ctx** out);
+void nwd_destroy(nwd_ctx* c);
+const char* nwd_last_error(const nwd_ctx* c);
+
+/* Builds the index of n_refs amplicons in HBM: amplicon g = refs[ref_offsets[g] ..
+ * ref_offsets[g + 1]) (HOST memory, offsets int64 [n_refs + 1] ascending).  1 <= n_refs <=
+ * NWD_MAX_REFS, ref_offsets[n_refs] - ref_offsets[0] <= NWD_MAX_REF_BASES, NWD_MIN_K <= k <=
+ * NWD_MAX_K; anything else is NW_E_UNSUPPORTED.  *n_windows = distinct windows in the index,
+ * *n_ambiguous = those of them that map to AMBIGUOUS (either may be NULL).  Replaces the
+ * context's previous index.  Synchronous. */
+int nwd_set_amplicons(nwd_ctx* c, const uint8_t* refs, const int64_t* ref_offsets, int64_t n_refs, int32_t k,
+                      int64_t* n_windows, int64_t* n_ambiguous);
+
+/* Assigns n reads held in HOST memory: read r = reads[offsets[r] .. offsets[r + 1]), offsets
+ * int64 [n + 1] ascending, 0 <= n <= 2^31 - 1.  A read longer than NWD_MAX_READ bases (the front
+ * end's limit) or min_hits < 1 is NW_E_UNSUPPORTED; a call before nwd_set_amplicons NW_E_STATE.
+ *
+ * Per-read outputs (HOST, each may be NULL): which int32 [n] (g, NWD_NO_HIT or NWD_TIE), strand
+ * uint8 [n], votes / rival int32 [n].  counts int64 [n_refs] (may be NULL): reads assigned to
+ * each amplicon.  *n_assigned + *n_tie + *n_no_hit = n (each may be NULL).  n == 0 returns zeros
+ * without touching the GPU.  kernel_ms (may be NULL): device time of the call's kernels.  The
+ * reads and the decisions stay on the device for nwd_gather until the next call.  Synchronous. */
+int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t n, int32_t min_hits,
+               int32_t both_strands, int32_t* which, uint8_t* strand, int32_t* votes, int32_t* rival,
+               int64_t* counts, int64_t* n_assigned, int64_t* n_tie, int64_t* n_no_hit, float* kernel_ms);
+
+/* The assigned reads of the last nwd_assign, grouped: group_offsets int64 [n_refs + 1] (group g
+ * is the gathered reads group_offsets[g] .. group_offsets[g + 1]), order int64 [n_assigned] the
+ * input index of each gathered read, text_offsets int64 [n_assigned + 1] into text [text_cap],
+ * the gathered bytes (strand-1 reads reverse-complemented on the device).  *needed (may be NULL)
+ * = the bytes text must hold; when text_cap is short the call returns NW_E_CAPACITY with
+ * *needed, group_offsets, order and text_offsets written (each may be NULL).  Synchronous. */
+int nwd_gather(nwd_ctx* c, int64_t* group_offsets, int64_t* order, uint8_t* text, int64_t* text_offsets,
+               int64_t text_cap, int64_t* needed);
+
+/* Reads of the last nwd_assign with more distinct candidates than the tally holds: they were
+ * decided by the exact path on the host (the same rule). */
+int64_t nwd_last_fallback(const nwd_ctx* c);
+
+/* Times of the last nwd_assign, summed over its chunks: ms[0] device ms of the assign kernel,
+ * ms[1] the host's wall ms in the chunks' uploads; ms[2] device ms of the last index build,
+ * ms[3] of the last gather kernel.  A diagnostic (scripts/bench_demux.py). */
+int nwd_phase_times(const nwd_ctx* c, float* ms);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
