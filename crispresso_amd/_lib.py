@@ -73,7 +73,7 @@ COUNT_EXPORTS = (
 # Every symbol include/crispr_demux.h declares.
 DEMUX_EXPORTS = (
     "nwd_create", "nwd_destroy", "nwd_last_error", "nwd_set_amplicons", "nwd_assign", "nwd_gather",
-    "nwd_last_fallback", "nwd_phase_times",
+    "nwd_last_fallback", "nwd_phase_times", "nwd_pack", "nwd_fetch_packed", "nwd_adopt_group",
 )
 NWD_NO_HIT, NWD_TIE = -1, -2
 
@@ -341,6 +341,9 @@ def load() -> ctypes.CDLL:
         "nwd_gather": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, POINTER(c_int64)]),
         "nwd_last_fallback": (c_int64, [ctx_p]),
         "nwd_phase_times": (c_int, [ctx_p, c_void_p]),
+        "nwd_pack": (c_int, [ctx_p] + [c_void_p] * 5 + [POINTER(c_int64), POINTER(c_float)]),
+        "nwd_fetch_packed": (c_int, [ctx_p, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
+        "nwd_adopt_group": (c_int, [ctx_p, ctx_p, c_int64]),
         "nwr_read_bam": (c_int, [c_char_p, c_void_p, c_int64, POINTER(c_void_p), c_char_p, c_int64]),
         "nwr_bam_free": (None, [c_void_p]),
         "nwr_bam_count": (c_int64, [c_void_p]),

@@ -236,6 +236,7 @@ class GpuAligner:
         )
         self.scale = int(self.lib.nw_score_scale(self._h))
         self.reference: Optional[str] = None
+        self.output_mode = "rows"   # of the upload/run path (set_output)
 
     def _check(self, rc: int, what: str) -> None:
         if rc != _lib.NW_OK:
@@ -393,6 +394,7 @@ class GpuAligner:
         """Output mode of the upload/run path: "rows" (default) or "ops"; from the next upload."""
         self._check(self.lib.nw_batch_set_output(self._h, _lib.NW_OUT_OPS if mode == "ops" else _lib.NW_OUT_ROWS),
                     "nw_batch_set_output")
+        self.output_mode = "ops" if mode == "ops" else "rows"
 
     def download_ops(self, n: int) -> OpsBatch:
         stats = np.zeros(n, dtype=_lib.STAT_DTYPE)

@@ -22,7 +22,20 @@
 //   gather   one wavefront per assigned read: its bytes copied, or reversed and complemented,
 //            to their place in the grouped text.  The counts' prefix sum and each read's rank in
 //            its group (ascending input index) are one pass of the host over `which`.
-// The reads are uploaded in chunks into one text buffer that stays resident for the gather.
+//   pack     nw_pack_reads (nw_pack.cpp) of the gathered text without that text: a thread a dword
+//            of the 2-bit stream.  It finds the read that holds gathered position 16 w by a
+//            bounded binary search of dst, takes its 16 bytes from the resident input (one 16-B
+//            load when they lie in one read; reversed for a strand-1 read, whose complement is
+//            code ^ 2), and writes the dword once, whole: an exception or a position past the end
+//            gives 0 bits.  The block's exceptions go to sums[]; one block scans the sums; if
+//            there are any, the exceptions kernel walks the same dwords and writes (position,
+//            byte) at the block's base + the block scan of the threads' counts: ascending
+//            positions, a function of the input alone.  No atomics, no zeroed buffer, nothing
+//            handed between blocks inside a launch.  Sums are 32-bit: 2^32 or more gathered
+//            bytes are refused.  bounds: a thread a group, the first exception at or after the
+//            group's first position (binary search of the exception list).
+// The reads are uploaded in chunks into one text buffer that stays resident for the gather, the
+// packer and, through nwd_adopt_group, the aligner (nw_front::set_packed_batch on a slice).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -36,8 +49,10 @@
 
 #include "../../include/crispr_demux.h"
 #include "../../include/crispr_nw.h"
+#include "front_device.h"
 #include "group_device.h"
 #include "host_dev.h"
+#include "nw_device.h"
 
 namespace nwd {
 
@@ -303,6 +318,196 @@ __global__ __launch_bounds__(256) void nwd_gather_kernel(const uint8_t* text, co
     for (int p = lane; p < n; p += 64) d[p] = rev ? complement(s[n - 1 - p]) : s[p];
 }
 
+// ---- the packer of the grouped reads -----------------------------------------------------------
+
+constexpr int kPackBlk = 256;      // dwords (threads) per block: 4096 gathered positions
+constexpr int kScanBlk = 1024;     // threads of the scan block
+
+__device__ __forceinline__ bool is_acgt(uint8_t b) {   // nw_pack.cpp's
+    const uint8_t u = b & 0xDF;
+    return u == 'A' || u == 'C' || u == 'G' || u == 'T';
+}
+
+struct PackArgs {
+    const uint8_t* text;        // the resident input (AssignArgs::text)
+    const int64_t* off;
+    int64_t base;
+    const uint64_t* src;        // [na]
+    const int64_t* dst;         // [na + 1]
+    int64_t na, total, nwords, blocks, n_exc;
+    uint32_t* words;            // [nwords]
+    uint32_t* sums;             // [blocks] exceptions of each block, then their exclusive prefix
+    int64_t* totals;            // [1]
+    int64_t* exc_pos;           // [n_exc]
+    uint8_t* exc_byte;
+};
+
+// Gathered positions 16 w .. 16 w + 15 in the gathered order: byte k of raw is the input byte that
+// position 16 w + k shows (not yet complemented), bit k of rev set when its read is strand 1,
+// have = the positions before the end of the gathered text (1..16).
+struct Piece {
+    uint64_t lo, hi;           // bytes 0..7 and 8..15
+    uint32_t rev;
+    int have;
+};
+
+__device__ __forceinline__ Piece piece_at(const PackArgs& a, int64_t w) {
+    Piece pc{0, 0, 0, 0};
+    const int64_t p0 = 16 * w;
+    const int64_t left = a.total - p0;                     // >= 1
+    pc.have = left < 16 ? (int)left : 16;
+    int64_t lo = 0, hi = a.na;                             // the last j with dst[j] <= p0: its read holds p0
+    while (hi - lo > 1) {                                  // (at most 31 steps: na < 2^31)
+        const int64_t mid = (lo + hi) >> 1;
+        if (a.dst[mid] <= p0) lo = mid; else hi = mid;
+    }
+    int64_t j = lo;
+    uint64_t sr = a.src[j];
+    int64_t r = (int64_t)(sr & ~(1ull << 63));
+    bool rev = (sr >> 63) != 0;
+    int64_t o0 = a.off[r] - a.base, d0 = a.dst[j], e = a.dst[j + 1];
+    if (p0 + 16 <= e) {                                    // all 16 in this read: one load
+        const int64_t q = p0 - d0, n = e - d0;
+        uint32_t in[4];
+        __builtin_memcpy(in, a.text + o0 + (rev ? n - q - 16 : q), 16);
+        if (rev) {
+            pc.lo = ((uint64_t)__builtin_bswap32(in[2]) << 32) | __builtin_bswap32(in[3]);
+            pc.hi = ((uint64_t)__builtin_bswap32(in[0]) << 32) | __builtin_bswap32(in[1]);
+            pc.rev = 0xFFFFu;
+        } else {
+            pc.lo = ((uint64_t)in[1] << 32) | in[0];
+            pc.hi = ((uint64_t)in[3] << 32) | in[2];
+        }
+        return pc;
+    }
+    for (int k = 0; k < pc.have; ++k) {                    // the end of one read and the start of the next
+        const int64_t p = p0 + k;
+        while (p >= e && j + 1 < a.na) {                   // (empty reads are stepped over)
+            ++j;
+            sr = a.src[j];
+            r = (int64_t)(sr & ~(1ull << 63));
+            rev = (sr >> 63) != 0;
+            o0 = a.off[r] - a.base;
+            d0 = e;
+            e = a.dst[j + 1];
+        }
+        const int64_t q = p - d0;
+        const uint8_t c = a.text[o0 + (rev ? (e - d0) - 1 - q : q)];
+        if (k < 8) pc.lo |= (uint64_t)c << (8 * k);
+        else pc.hi |= (uint64_t)c << (8 * (k - 8));
+        pc.rev |= (rev ? 1u : 0u) << k;
+    }
+    return pc;
+}
+
+__device__ __forceinline__ uint8_t piece_byte(const Piece& pc, int k) {
+    return (uint8_t)(k < 8 ? pc.lo >> (8 * k) : pc.hi >> (8 * (k - 8)));
+}
+
+__global__ __launch_bounds__(kPackBlk) void nwd_pack_words_kernel(const PackArgs a) {
+    __shared__ uint32_t part[kPackBlk / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t w = (int64_t)blockIdx.x * kPackBlk + threadIdx.x;
+    uint32_t ne = 0;
+    if (w < a.nwords) {
+        const Piece pc = piece_at(a, w);
+        uint32_t out = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint8_t c = piece_byte(pc, k);
+            if (k < pc.have) {
+                // the complement of a base is its code ^ 2 (A C T G = 0 1 2 3)
+                if (is_acgt(c)) out |= ((uint32_t)((c >> 1) & 3) ^ (((pc.rev >> k) & 1u) << 1)) << (2 * k);
+                else ++ne;
+            }
+        }
+        a.words[w] = out;
+    }
+    for (int s = 32; s > 0; s >>= 1) ne += __shfl_xor(ne, s);
+    if (lane == 0) part[wave] = ne;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int v = 0; v < kPackBlk / 64; ++v) s += part[v];
+        a.sums[blockIdx.x] = s;
+    }
+}
+
+// One block: sums[b] becomes the exclusive prefix over the blocks before b; totals[0] the sum.
+__global__ __launch_bounds__(kScanBlk) void nwd_pack_scan_kernel(const PackArgs a) {
+    __shared__ uint32_t sh[2][kScanBlk];
+    const int t = threadIdx.x;
+    const int64_t per = (a.blocks + kScanBlk - 1) / kScanBlk;
+    const int64_t lo = std::min<int64_t>(a.blocks, t * per), hi = std::min<int64_t>(a.blocks, lo + per);
+    uint32_t mine = 0;
+    for (int64_t b = lo; b < hi; ++b) mine += a.sums[b];
+    int cur = 0;
+    sh[0][t] = mine;
+    __syncthreads();
+    for (int d = 1; d < kScanBlk; d <<= 1) {               // inclusive scan of the threads' sums
+        sh[cur ^ 1][t] = sh[cur][t] + (t >= d ? sh[cur][t - d] : 0u);
+        cur ^= 1;
+        __syncthreads();
+    }
+    uint32_t run = sh[cur][t] - mine;
+    if (t == kScanBlk - 1) a.totals[0] = (int64_t)sh[cur][t];
+    for (int64_t b = lo; b < hi; ++b) {
+        const uint32_t v = a.sums[b];
+        a.sums[b] = run;
+        run += v;
+    }
+}
+
+// The exceptions in ascending position: the slot of a thread's first one is the block's base +
+// the exceptions of the block's threads before it.
+__global__ __launch_bounds__(kPackBlk) void nwd_pack_exc_kernel(const PackArgs a) {
+    __shared__ uint32_t part[kPackBlk / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t w = (int64_t)blockIdx.x * kPackBlk + threadIdx.x;
+    Piece pc{0, 0, 0, 0};
+    uint32_t ne = 0;
+    if (w < a.nwords) {
+        pc = piece_at(a, w);
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k < pc.have && !is_acgt(piece_byte(pc, k))) ++ne;
+    }
+    uint32_t x = ne;
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t y = __shfl_up(x, s);
+        if (lane >= s) x += y;
+    }
+    if (lane == 63) part[wave] = x;
+    __syncthreads();
+    int64_t slot = (int64_t)a.sums[blockIdx.x] + (x - ne);
+    for (int v = 0; v < wave; ++v) slot += part[v];
+    if (ne == 0) return;
+    for (int k = 0; k < pc.have; ++k) {
+        const uint8_t c = piece_byte(pc, k);
+        if (is_acgt(c)) continue;
+        if (slot < a.n_exc) {                              // (always: the count kernel's sum)
+            a.exc_pos[slot] = 16 * w + k;
+            a.exc_byte[slot] = c;                          // (complement leaves every such byte as it is)
+        }
+        ++slot;
+    }
+}
+
+// gexc[g] = the exceptions before group g's first position, g in [0, ng]: group g's are the slots
+// gexc[g] .. gexc[g + 1].
+__global__ __launch_bounds__(256) void nwd_pack_bounds_kernel(const int64_t* exc_pos, int64_t n_exc, const int64_t* dst,
+                                                              const int64_t* goff, int64_t ng, int64_t* gexc) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g > ng) return;
+    const int64_t pos = dst[goff[g]];
+    int64_t lo = 0, hi = n_exc;                            // the first slot with exc_pos >= pos
+    while (lo < hi) {
+        const int64_t mid = (lo + hi) >> 1;
+        if (exc_pos[mid] < pos) lo = mid + 1; else hi = mid;
+    }
+    gexc[g] = lo;
+}
+
 }  // namespace nwd
 
 struct nwd_ctx : hd::DevContext {
@@ -323,6 +528,19 @@ struct nwd_ctx : hd::DevContext {
     std::vector<uint8_t> strand;
     std::vector<int64_t> counts;
     float phase_ms[4] = {0, 0, 0, 0};
+    // the groups of the last assign (group_layout): one host pass, shared by the gather and the packer
+    bool layout_ok = false;
+    std::vector<int64_t> goff, dst;
+    std::vector<uint64_t> src;     // input index, bit 63 = strand
+    // the last pack: valid until the next nwd_assign / nwd_set_amplicons
+    bool packed_ok = false;
+    int64_t pk_total = 0, pk_n_exc = 0;
+    std::vector<uint16_t> lens16;
+    std::vector<int64_t> gexc;
+    hd::DevBuf<uint32_t> d_words, d_sums;
+    hd::DevBuf<uint16_t> d_lens16;
+    hd::DevBuf<int64_t> d_totals, d_exc_pos, d_goff, d_gexc, d_gbase;
+    hd::DevBuf<uint8_t> d_exc_byte;
     hd::DevBuf<unsigned long long> d_tab;
     hd::DevBuf<uint8_t> d_refs, d_text, d_strand, d_out;
     hd::DevBuf<int64_t> d_roff, d_off, d_dst;
@@ -385,12 +603,37 @@ void decide_on_host(nwd_ctx* c, const uint8_t* s, int n, int min_hits, bool both
     *rival = riv;
 }
 
+// The groups of the last assign, one pass of the host over `which` (kept until the next assign):
+// goff by a prefix sum of the counts, src[j] = the input index of gathered read j (ascending in
+// its group) with bit 63 as its strand, dst [na + 1] the gathered offsets.
+void group_layout(nwd_ctx* c) {
+    if (c->layout_ok) return;
+    const int64_t n = c->n, ng = c->n_refs;
+    c->goff.assign((size_t)ng + 1, 0);
+    if (c->counts.size() == (size_t)ng)
+        for (int64_t g = 0; g < ng; ++g) c->goff[(size_t)g + 1] = c->goff[(size_t)g] + c->counts[(size_t)g];
+    const int64_t na = c->goff[(size_t)ng];
+    std::vector<int64_t> next(c->goff.begin(), c->goff.end() - 1);
+    c->dst.assign((size_t)na + 1, 0);
+    c->src.resize((size_t)na);
+    for (int64_t r = 0; r < n; ++r) {
+        const int32_t g = c->which[(size_t)r];
+        if (g < 0) continue;
+        c->src[(size_t)next[(size_t)g]++] = (uint64_t)r | ((uint64_t)(c->strand[(size_t)r] & 1) << 63);
+    }
+    for (int64_t j = 0; j < na; ++j) {
+        const int64_t r = (int64_t)(c->src[(size_t)j] & ~(1ull << 63));
+        c->dst[(size_t)j + 1] = c->dst[(size_t)j] + (c->off[(size_t)r + 1] - c->off[(size_t)r]);
+    }
+    c->layout_ok = true;
+}
+
 }  // namespace
 
 extern "C" {
 
 int nwd_create(int device, nwd_ctx** out) {
-    const int rc = hd::create_context(device, 2, out);
+    const int rc = hd::create_context(device, 3, out);      // ev[2]: recorded behind the last packer
     if (rc != NW_OK) return rc;
     nwd_ctx* c = *out;
     if (const char* e = std::getenv("CRISPR_NWD_CHUNK"))
@@ -430,6 +673,7 @@ int nwd_set_amplicons(nwd_ctx* c, const uint8_t* refs, const int64_t* ref_offset
     c->k = 0;                      // no index until this call succeeds
     c->n_refs = 0;
     c->n = 0;
+    c->layout_ok = c->packed_ok = false;
     c->which.clear();
     c->strand.clear();
     c->counts.clear();
@@ -501,6 +745,7 @@ int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t
                         (long long)len, NWD_MAX_READ);
     }
     c->n = 0;
+    c->layout_ok = c->packed_ok = false;
     c->fallback = 0;
     c->phase_ms[0] = c->phase_ms[1] = 0.0f;
     c->which.assign((size_t)n, NWD_NO_HIT);
@@ -626,24 +871,12 @@ int nwd_gather(nwd_ctx* c, int64_t* group_offsets, int64_t* order, uint8_t* text
     if (!c) return NW_E_INVALID;
     if (c->k == 0) return fail(c, NW_E_STATE, "nwd_gather before nwd_set_amplicons");
     if (text_cap < 0) return fail(c, NW_E_INVALID, "negative capacity");
-    const int64_t n = c->n, ng = c->n_refs;
+    const int64_t ng = c->n_refs;
     c->phase_ms[3] = 0.0f;
-    // the groups' offsets by a prefix sum of the counts; each read's rank from its input index
-    std::vector<int64_t> goff((size_t)ng + 1, 0);
-    if (c->counts.size() == (size_t)ng)
-        for (int64_t g = 0; g < ng; ++g) goff[(size_t)g + 1] = goff[(size_t)g] + c->counts[(size_t)g];
+    group_layout(c);
+    const std::vector<int64_t>&goff = c->goff, &dst = c->dst;
+    const std::vector<uint64_t>& src = c->src;
     const int64_t na = goff[(size_t)ng];
-    std::vector<int64_t> next(goff.begin(), goff.end() - 1), dst((size_t)na + 1, 0);
-    std::vector<uint64_t> src((size_t)na);
-    for (int64_t r = 0; r < n; ++r) {
-        const int32_t g = c->which[(size_t)r];
-        if (g < 0) continue;
-        src[(size_t)next[(size_t)g]++] = (uint64_t)r | ((uint64_t)(c->strand[(size_t)r] & 1) << 63);
-    }
-    for (int64_t j = 0; j < na; ++j) {
-        const int64_t r = (int64_t)(src[(size_t)j] & ~(1ull << 63));
-        dst[(size_t)j + 1] = dst[(size_t)j] + (c->off[(size_t)r + 1] - c->off[(size_t)r]);
-    }
     const int64_t nbytes = dst[(size_t)na];
     if (needed) *needed = nbytes;
     if (group_offsets) std::memcpy(group_offsets, goff.data(), sizeof(int64_t) * (size_t)(ng + 1));
@@ -669,6 +902,150 @@ int nwd_gather(nwd_ctx* c, int64_t* group_offsets, int64_t* order, uint8_t* text
     HIP_TRY(c, hipMemcpyAsync(text, c->d_out.p, (size_t)nbytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(c, hipStreamSynchronize(st));      // (src and dst above are read by the copies)
     HIP_TRY(c, hipEventElapsedTime(&c->phase_ms[3], c->ev[0], c->ev[1]));
+    return NW_OK;
+}
+
+int nwd_pack(nwd_ctx* c, int64_t* group_offsets, int64_t* order, int64_t* text_offsets, uint16_t* lens,
+             int64_t* group_exc, int64_t* n_exc, float* kernel_ms) {
+    if (!c) return NW_E_INVALID;
+    if (c->k == 0) return fail(c, NW_E_STATE, "nwd_pack before nwd_set_amplicons");
+    const int64_t ng = c->n_refs;
+    c->packed_ok = false;
+    group_layout(c);
+    const int64_t na = c->goff[(size_t)ng], total = c->dst[(size_t)na];
+    if ((uint64_t)total >= (1ull << 32))
+        return fail(c, NW_E_UNSUPPORTED, "%lld gathered bytes: 2^32 or more in one call are not supported",
+                    (long long)total);
+    c->lens16.resize((size_t)na);
+    for (int64_t j = 0; j < na; ++j) c->lens16[(size_t)j] = (uint16_t)(c->dst[(size_t)j + 1] - c->dst[(size_t)j]);
+    c->gexc.assign((size_t)ng + 1, 0);
+    c->pk_total = total;
+    c->pk_n_exc = 0;
+    float ms_a = 0.0f, ms_b = 0.0f;
+    if (total > 0) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        hipStream_t st = c->stream;
+        nwd::PackArgs a{};
+        a.na = na;
+        a.total = total;
+        a.nwords = (total + 15) / 16;
+        a.blocks = (a.nwords + nwd::kPackBlk - 1) / nwd::kPackBlk;
+        HIP_TRY(c, c->d_src.reserve((size_t)na));
+        HIP_TRY(c, c->d_dst.reserve((size_t)na + 1));
+        HIP_TRY(c, c->d_lens16.reserve((size_t)na));
+        HIP_TRY(c, c->d_goff.reserve((size_t)ng + 1));
+        HIP_TRY(c, c->d_gexc.reserve((size_t)ng + 1));
+        HIP_TRY(c, c->d_words.reserve((size_t)a.nwords + 16));      // (the adoption's copies stay inside)
+        HIP_TRY(c, c->d_sums.reserve((size_t)a.blocks));
+        HIP_TRY(c, c->d_totals.reserve(1));
+        HIP_TRY(c, hipMemcpyAsync(c->d_src.p, c->src.data(), sizeof(uint64_t) * (size_t)na, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->d_dst.p, c->dst.data(), sizeof(int64_t) * (size_t)(na + 1), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->d_lens16.p, c->lens16.data(), sizeof(uint16_t) * (size_t)na, hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipMemcpyAsync(c->d_goff.p, c->goff.data(), sizeof(int64_t) * (size_t)(ng + 1), hipMemcpyHostToDevice, st));
+        a.text = c->d_text.p;
+        a.off = c->d_off.p;
+        a.base = c->base;
+        a.src = c->d_src.p;
+        a.dst = c->d_dst.p;
+        a.words = c->d_words.p;
+        a.sums = c->d_sums.p;
+        a.totals = c->d_totals.p;
+        HIP_TRY(c, hipEventRecord(c->ev[0], st));
+        hipLaunchKernelGGL(nwd::nwd_pack_words_kernel, dim3((unsigned)a.blocks), dim3(nwd::kPackBlk), 0, st, a);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(nwd::nwd_pack_scan_kernel, dim3(1), dim3(nwd::kScanBlk), 0, st, a);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->ev[1], st));
+        int64_t ne = 0;
+        HIP_TRY(c, hipMemcpyAsync(&ne, a.totals, sizeof ne, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        HIP_TRY(c, hipEventElapsedTime(&ms_a, c->ev[0], c->ev[1]));
+        if (ne < 0 || ne > total) return fail(c, NW_E_STATE, "inconsistent exception count");
+        if (ne > 0) {      // (none: the exceptions kernel is skipped)
+            HIP_TRY(c, c->d_exc_pos.reserve((size_t)ne));
+            HIP_TRY(c, c->d_exc_byte.reserve((size_t)ne));
+            a.n_exc = ne;
+            a.exc_pos = c->d_exc_pos.p;
+            a.exc_byte = c->d_exc_byte.p;
+            HIP_TRY(c, hipEventRecord(c->ev[0], st));
+            hipLaunchKernelGGL(nwd::nwd_pack_exc_kernel, dim3((unsigned)a.blocks), dim3(nwd::kPackBlk), 0, st, a);
+            HIP_TRY(c, hipGetLastError());
+            hipLaunchKernelGGL(nwd::nwd_pack_bounds_kernel, dim3((unsigned)((ng + 1 + 255) / 256)), dim3(256), 0, st,
+                               (const int64_t*)a.exc_pos, ne, a.dst, (const int64_t*)c->d_goff.p, ng, c->d_gexc.p);
+            HIP_TRY(c, hipGetLastError());
+            HIP_TRY(c, hipEventRecord(c->ev[1], st));
+            HIP_TRY(c, hipMemcpyAsync(c->gexc.data(), c->d_gexc.p, sizeof(int64_t) * (size_t)(ng + 1), hipMemcpyDeviceToHost, st));
+            HIP_TRY(c, hipEventRecord(c->ev[2], st));
+            HIP_TRY(c, hipStreamSynchronize(st));
+            HIP_TRY(c, hipEventElapsedTime(&ms_b, c->ev[0], c->ev[1]));
+        } else {
+            HIP_TRY(c, hipEventRecord(c->ev[2], st));
+        }
+        c->pk_n_exc = ne;
+    }
+    if (group_offsets) std::memcpy(group_offsets, c->goff.data(), sizeof(int64_t) * (size_t)(ng + 1));
+    if (order)
+        for (int64_t j = 0; j < na; ++j) order[j] = (int64_t)(c->src[(size_t)j] & ~(1ull << 63));
+    if (text_offsets) std::memcpy(text_offsets, c->dst.data(), sizeof(int64_t) * (size_t)(na + 1));
+    if (lens && na > 0) std::memcpy(lens, c->lens16.data(), sizeof(uint16_t) * (size_t)na);
+    if (group_exc) std::memcpy(group_exc, c->gexc.data(), sizeof(int64_t) * (size_t)(ng + 1));
+    if (n_exc) *n_exc = c->pk_n_exc;
+    if (kernel_ms) *kernel_ms = ms_a + ms_b;
+    c->packed_ok = true;
+    return NW_OK;
+}
+
+int nwd_fetch_packed(nwd_ctx* c, uint8_t* packed, int64_t cap, int64_t* exc_pos, uint8_t* exc_byte, int64_t* needed) {
+    if (!c) return NW_E_INVALID;
+    if (!c->packed_ok) return fail(c, NW_E_STATE, "nwd_fetch_packed before nwd_pack");
+    const int64_t nbytes = (c->pk_total + 3) / 4, ne = c->pk_n_exc;
+    if (needed) *needed = nbytes;
+    if (cap < nbytes)
+        return fail(c, NW_E_CAPACITY, "%lld packed bytes, capacity %lld", (long long)nbytes, (long long)cap);
+    if (nbytes == 0) return NW_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    if (packed) HIP_TRY(c, hipMemcpyAsync(packed, c->d_words.p, (size_t)nbytes, hipMemcpyDeviceToHost, st));
+    if (exc_pos && ne > 0) HIP_TRY(c, hipMemcpyAsync(exc_pos, c->d_exc_pos.p, sizeof(int64_t) * (size_t)ne, hipMemcpyDeviceToHost, st));
+    if (exc_byte && ne > 0) HIP_TRY(c, hipMemcpyAsync(exc_byte, c->d_exc_byte.p, (size_t)ne, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    return NW_OK;
+}
+
+int nwd_adopt_group(nwd_ctx* c, nw_ctx* ctx, int64_t g) {
+    if (!c) return NW_E_INVALID;
+    if (!ctx) return fail(c, NW_E_INVALID, "null aligner context");
+    if (!c->packed_ok) return fail(c, NW_E_STATE, "nwd_adopt_group before nwd_pack");
+    if (g < 0 || g >= c->n_refs)
+        return fail(c, NW_E_INVALID, "group %lld: there are %lld amplicons", (long long)g, (long long)c->n_refs);
+    const int64_t j0 = c->goff[(size_t)g], m = c->goff[(size_t)g + 1] - j0;
+    if (m <= 0) return fail(c, NW_E_INVALID, "group %lld holds no read", (long long)g);
+    int rc = nw_front::check_state(ctx);
+    if (rc != NW_OK) return fail(c, rc, "the aligner context: %s", nw_last_error(ctx));
+    if (nw_front::device_of(ctx) != c->device)
+        return fail(c, NW_E_INVALID, "the aligner context is on device %d, the reads on device %d",
+                    nw_front::device_of(ctx), c->device);
+    HIP_TRY(c, hipSetDevice(c->device));
+    // every kLenGroup-th offset counted from the group's own first read (a group does not start
+    // on a multiple of kLenGroup of the whole call)
+    const int64_t ngroups = m / nw::kLenGroup + 1;
+    std::vector<int64_t> gb((size_t)ngroups);
+    for (int64_t q = 0; q < ngroups; ++q) gb[(size_t)q] = c->dst[(size_t)(j0 + q * nw::kLenGroup)];
+    HIP_TRY(c, c->d_gbase.reserve((size_t)ngroups));
+    HIP_TRY(c, hipMemcpyAsync(c->d_gbase.p, gb.data(), sizeof(int64_t) * (size_t)ngroups, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const int64_t e0 = c->gexc[(size_t)g], ne = c->gexc[(size_t)g + 1] - e0;
+    // the whole call's stream and the group's slice of the exceptions, both in gathered
+    // coordinates: set_packed_batch copies bytes offsets[0] / 4 .. (offsets[m] + 3) / 4 of it
+    const nw_front::PackedSrc src{(const uint8_t*)c->d_words.p,
+                                  c->d_lens16.p + j0,
+                                  c->d_gbase.p,
+                                  ne > 0 ? c->d_exc_pos.p + e0 : nullptr,
+                                  ne > 0 ? c->d_exc_byte.p + e0 : nullptr,
+                                  true,
+                                  c->ev[2]};
+    rc = nw_front::set_packed_batch(ctx, src, c->dst.data() + j0, c->lens16.data() + j0, m, ne);
+    if (rc != NW_OK) return fail(c, rc, "the aligner context: %s", nw_last_error(ctx));
     return NW_OK;
 }
 

@@ -10,6 +10,8 @@ as no hit, not guessed.
 
 * :func:`demultiplex`         -- amplicons + reads -> :class:`DemuxResult`
 * :func:`align_demultiplexed` -- the same, then :func:`crispresso_amd.pooled.align_pooled`
+* :func:`align_demultiplexed_resident` -- assigned, grouped and 2-bit packed in HBM, each group
+  adopted by the aligner where it lies; only decisions, records and runs cross PCIe
 * :func:`read_amplicons_file` -- the reference's tab-separated amplicon table
 * ``python -m crispresso_amd.demux`` -- FASTQ + amplicon table -> per-amplicon FASTQ files and
   the reference's ``REPORT_READS_ALIGNED_TO_AMPLICONS.txt``
@@ -126,6 +128,19 @@ class DemuxResult:
         return out
 
 
+@dataclass
+class PackedGroups:
+    """One :meth:`GpuDemultiplexer.pack`: where the grouped reads lie in the packed batch in HBM."""
+
+    group_offsets: np.ndarray          # int64 [amplicons + 1]
+    order: np.ndarray                  # int64 [n_assigned]
+    text_offsets: np.ndarray           # int64 [n_assigned + 1]: gathered coordinates
+    lens: np.ndarray                   # uint16 [n_assigned]
+    group_exc: np.ndarray              # int64 [amplicons + 1]: group g's slots of the exception list
+    n_exc: int
+    kernel_ms: float
+
+
 class GpuDemultiplexer:
     """One ``nwd_ctx`` (one GPU), reusable across calls and amplicon sets.  Not thread-safe."""
 
@@ -139,6 +154,7 @@ class GpuDemultiplexer:
         self.device = device
         self.n_amplicons = 0
         self.n_windows = self.n_ambiguous = 0
+        self._packed: Optional[PackedGroups] = None
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):
@@ -173,6 +189,7 @@ class GpuDemultiplexer:
     def set_amplicons(self, buf: np.ndarray, offsets: np.ndarray, k: int) -> Tuple[int, int]:
         nw, na = ctypes.c_int64(), ctypes.c_int64()
         n = len(offsets) - 1
+        self._packed = None
         self._check(self._lib.nwd_set_amplicons(self._ctx, _lib.ptr(buf), _lib.ptr(offsets), n, k, ctypes.byref(nw),
                                                 ctypes.byref(na)), "nwd_set_amplicons")
         self.n_amplicons, self.n_windows, self.n_ambiguous = n, int(nw.value), int(na.value)
@@ -185,6 +202,7 @@ class GpuDemultiplexer:
         counts = np.zeros(self.n_amplicons, np.int64)
         na, nt, nn = (ctypes.c_int64() for _ in range(3))
         ms = ctypes.c_float()
+        self._packed = None
         self._check(self._lib.nwd_assign(self._ctx, _lib.ptr(buf), _lib.ptr(offsets), n, min_hits, int(bool(both_strands)),
                                          _lib.ptr(which), _lib.ptr(strand), _lib.ptr(votes), _lib.ptr(rival),
                                          _lib.ptr(counts), ctypes.byref(na), ctypes.byref(nt), ctypes.byref(nn),
@@ -208,6 +226,42 @@ class GpuDemultiplexer:
                                       text_cap, ctypes.byref(need))
         self._check(rc, "nwd_gather")
         return goff, order, text[:int(need.value)], toff
+
+    def pack(self, n_assigned: int) -> "PackedGroups":
+        """The grouped reads of the last :meth:`assign` 2-bit packed in HBM (``nwd_pack``): the
+        index arrays :meth:`gather` gives, the lengths and each group's slice of the exception
+        list.  The gathered text is not made; nothing but these small arrays crosses PCIe."""
+        goff = np.zeros(self.n_amplicons + 1, np.int64)
+        order = np.empty(n_assigned, np.int64)
+        toff = np.zeros(n_assigned + 1, np.int64)
+        lens = np.empty(n_assigned, np.uint16)
+        gexc = np.zeros(self.n_amplicons + 1, np.int64)
+        ne, ms = ctypes.c_int64(), ctypes.c_float()
+        self._check(self._lib.nwd_pack(self._ctx, _lib.ptr(goff), _lib.ptr(order), _lib.ptr(toff), _lib.ptr(lens),
+                                       _lib.ptr(gexc), ctypes.byref(ne), ctypes.byref(ms)), "nwd_pack")
+        self._packed = PackedGroups(goff, order, toff, lens, gexc, int(ne.value), float(ms.value))
+        return self._packed
+
+    def fetch_packed(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(packed, exc_pos, exc_byte) of the last :meth:`pack`, copied to the host (for tests)."""
+        pk = self._packed
+        if pk is None:
+            raise DemuxError("fetch_packed before pack")
+        nbytes = (int(pk.text_offsets[-1]) + 3) // 4
+        packed = np.zeros(max(nbytes, 1), np.uint8)
+        pos, byt = np.empty(pk.n_exc, np.int64), np.empty(pk.n_exc, np.uint8)
+        self._check(self._lib.nwd_fetch_packed(self._ctx, _lib.ptr(packed), nbytes, _lib.ptr(pos), _lib.ptr(byt), None),
+                    "nwd_fetch_packed")
+        return packed[:nbytes], pos, byt
+
+    def adopt(self, aligner, g: int) -> int:
+        """Make group ``g`` of the last :meth:`pack` the resident batch of ``aligner`` (ops output,
+        its reference set): ``nwd_adopt_group``.  Returns the group's number of reads."""
+        self._check(self._lib.nwd_adopt_group(self._ctx, aligner._h, int(g)), "nwd_adopt_group")
+        pk = self._packed
+        lo, hi = int(pk.group_offsets[g]), int(pk.group_offsets[g + 1])
+        aligner.adopted(None, pk.text_offsets[lo:hi + 1])
+        return hi - lo
 
 
 _DEFAULT: Dict[int, GpuDemultiplexer] = {}
@@ -259,6 +313,60 @@ def align_demultiplexed(amplicons: Sequence[str], reads, aligner, *, min_reads: 
     if keep:
         for g, b in zip(keep, align_pooled([amplicons[g] for g in keep], [groups[g] for g in keep], aligner)):
             batches[g] = b
+    return batches, res, skipped
+
+
+def align_demultiplexed_resident(amplicons: Sequence[str], reads, aligner, *, min_reads: int = 0, on_group=None,
+                                 with_text: bool = False, k: int = 16, min_hits: int = 2, both_strands: bool = True,
+                                 demultiplexer: Optional[GpuDemultiplexer] = None):
+    """:func:`align_demultiplexed` without the round trip: the reads are uploaded once, assigned,
+    oriented, grouped and 2-bit packed in HBM (``nwd_pack``), and each amplicon's group is adopted
+    by ``aligner`` where it lies (``nwd_adopt_group``) and aligned there.  Only the decisions,
+    the records and the runs cross PCIe.
+
+    For every amplicon with more than ``min_reads`` reads (strictly), in index order:
+    ``set_reference``, adoption, one synchronised pass, ``on_group(g, aligner, n)`` while the
+    group is resident (the place for ``quantify.run_device_ops`` or ``alleles.allele_table`` on
+    ``aligner.device_ops()``), ``download_ops``.
+
+    Returns ``(ops_batches, result, skipped)``: one :class:`~crispresso_amd.aligner.OpsBatch` per
+    amplicon (``None`` for a skipped one; ``OpsBatch.expand(amplicons[g], text, offsets)`` on the
+    group's text gives :func:`align_demultiplexed`'s rows), the :class:`DemuxResult` (``text``
+    filled only with ``with_text``, by ``nwd_gather``) and the skipped indices.  ``aligner`` must
+    be on the demultiplexer's device; its output mode is ops during the call and restored after."""
+    k, min_hits = check_params(k, min_hits)
+    abuf, aoff = pack_amplicons(amplicons)
+    rbuf, roff = _packed(reads)
+    check_offsets(rbuf, roff, "reads", MAX_READ)
+    if len(roff) - 1 > 2 ** 31 - 1:
+        raise ValueError("more than 2^31 - 1 reads")
+    d = demultiplexer or default_demultiplexer(getattr(aligner, "device", 0))
+    n_windows, n_ambiguous = d.set_amplicons(abuf, aoff, k)
+    which, strand, votes, rival, counts, na, nt, nn, ms = d.assign(rbuf, roff, min_hits, both_strands)
+    pk = d.pack(na)
+    if with_text:
+        _, _, text, _ = d.gather(na, int(pk.text_offsets[-1]))
+    else:
+        text = np.zeros(0, np.uint8)
+    res = DemuxResult(which, strand, votes, rival, counts, pk.group_offsets, pk.order, text, pk.text_offsets,
+                      n_windows, n_ambiguous, nt, nn, d.last_fallback(), ms, d.phase_times()["upload_wall"])
+    min_reads = max(int(min_reads), 0)      # (an amplicon without a read has nothing to adopt)
+    keep = [g for g in range(len(amplicons)) if int(counts[g]) > min_reads]
+    skipped = [g for g in range(len(amplicons)) if int(counts[g]) <= min_reads]
+    batches: list = [None] * len(amplicons)
+    mode = getattr(aligner, "output_mode", "rows")
+    aligner.set_output("ops")
+    try:
+        for g in keep:
+            aligner.set_reference(amplicons[g])
+            n = d.adopt(aligner, g)
+            aligner.run_async()
+            aligner.sync()
+            if on_group is not None:
+                on_group(g, aligner, n)
+            batches[g] = aligner.download_ops(n)
+    finally:
+        aligner.set_output(mode)
     return batches, res, skipped
 
 

@@ -98,6 +98,41 @@ int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t
 int nwd_gather(nwd_ctx* c, int64_t* group_offsets, int64_t* order, uint8_t* text, int64_t* text_offsets,
                int64_t text_cap, int64_t* needed);
 
+/* The grouped reads of the last nwd_assign as a packed batch in HBM, without the gathered text:
+ * exactly what nw_pack_reads (include/crispr_nw.h) makes of nwd_gather's text and text_offsets.
+ * Position text_offsets[j] + p is base p of gathered read j (a strand-1 read reversed and
+ * complemented on the fly).  The 2-bit stream holds 16 bases a dword, base i in bits 2 (i % 4) of
+ * byte i / 4, A C T G = 0 1 2 3; every byte that is none of A C G T a c g t is an exception
+ * (position and the byte itself, ascending; complementing leaves such a byte as it is) and gives
+ * 0 bits, as does a position past the end.  The stream is defined up to byte
+ * (text_offsets[n_assigned] + 3) / 4.
+ *
+ * Host outputs, each may be NULL: group_offsets, order and text_offsets as nwd_gather gives them;
+ * lens uint16 [n_assigned]; group_exc int64 [n_refs + 1]: group g's exceptions are the slots
+ * group_exc[g] .. group_exc[g + 1] of the list; *n_exc their number; *kernel_ms the device time of
+ * the packer's kernels.  NW_E_STATE before nwd_set_amplicons; 2^32 or more gathered bytes are
+ * NW_E_UNSUPPORTED.  With no assigned read it returns zeros and launches nothing.  The packed
+ * arrays stay in HBM until the next nwd_assign or nwd_set_amplicons (nwd_gather and
+ * nwd_adopt_group leave them alone).  The result is a function of the input alone.  Synchronous. */
+int nwd_pack(nwd_ctx* c, int64_t* group_offsets, int64_t* order, int64_t* text_offsets, uint16_t* lens,
+             int64_t* group_exc, int64_t* n_exc, float* kernel_ms);
+
+/* The last nwd_pack's stream and exception list copied to the HOST (for tests): packed [cap]
+ * bytes, exc_pos int64 [n_exc], exc_byte uint8 [n_exc] (each may be NULL).  *needed (may be NULL)
+ * = (text_offsets[n_assigned] + 3) / 4; a shorter cap is NW_E_CAPACITY with *needed written and
+ * nothing copied.  NW_E_STATE before nwd_pack. */
+int nwd_fetch_packed(nwd_ctx* c, uint8_t* packed, int64_t cap, int64_t* exc_pos, uint8_t* exc_byte, int64_t* needed);
+
+/* Makes group g of the last nwd_pack the resident batch of the aligner context `ctx`, as
+ * nw_batch_upload_packed would from the host: the group's lengths, its slice of the exception
+ * list and its part of the shared stream are copied device to device on ctx's stream, behind the
+ * packer.  Nothing crosses PCIe but the group's few group-base offsets.  ctx needs a reference
+ * and NW_OUT_OPS (else NW_E_STATE, as nw_batch_upload_packed) and must be on this context's
+ * device (NW_E_INVALID).  g outside [0, n_refs) or a group without reads is NW_E_INVALID; a call
+ * before nwd_pack NW_E_STATE.  A refusal leaves both contexts as they were.  Adopting a group
+ * does not change the packed arrays: groups may be adopted in any order, any number of times. */
+int nwd_adopt_group(nwd_ctx* c, struct nw_ctx* ctx, int64_t g);
+
 /* Reads of the last nwd_assign with more distinct candidates than the tally holds: they were
  * decided by the exact path on the host (the same rule). */
 int64_t nwd_last_fallback(const nwd_ctx* c);
