@@ -74,8 +74,17 @@ COUNT_EXPORTS = (
 DEMUX_EXPORTS = (
     "nwd_create", "nwd_destroy", "nwd_last_error", "nwd_set_amplicons", "nwd_assign", "nwd_gather",
     "nwd_last_fallback", "nwd_phase_times", "nwd_pack", "nwd_fetch_packed", "nwd_adopt_group",
+    "nwd_assign_prepared",
 )
 NWD_NO_HIT, NWD_TIE = -1, -2
+
+# Every symbol include/crispr_summary.h declares.
+SUMMARY_EXPORTS = ("nws_create", "nws_destroy", "nws_last_error", "nws_set_identity", "nws_flags", "nws_summary")
+NWS_SLOTS = 16
+# The slots of nws_summary's output, in order (the enum of include/crispr_summary.h).
+NWS_SLOT_NAMES = ("n", "n_total", "n_unmodified", "n_modified", "n_repaired", "n_mixed_hdr_nhej",
+                  "nhej_inserted", "nhej_deleted", "nhej_mutated", "hdr_inserted", "hdr_deleted", "hdr_mutated",
+                  "mixed_inserted", "mixed_deleted", "mixed_mutated", "not_aligned")
 
 # Every symbol include/crispr_regions.h declares.
 REGION_EXPORTS = (
@@ -344,6 +353,14 @@ def load() -> ctypes.CDLL:
         "nwd_pack": (c_int, [ctx_p] + [c_void_p] * 5 + [POINTER(c_int64), POINTER(c_float)]),
         "nwd_fetch_packed": (c_int, [ctx_p, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
         "nwd_adopt_group": (c_int, [ctx_p, ctx_p, c_int64]),
+        "nwd_assign_prepared": (c_int, [ctx_p, POINTER(NwpResult), c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                        c_void_p, c_void_p] + [POINTER(c_int64)] * 3 + [POINTER(c_float)]),
+        "nws_create": (c_int, [c_int, POINTER(c_void_p)]),
+        "nws_destroy": (None, [ctx_p]),
+        "nws_last_error": (c_char_p, [ctx_p]),
+        "nws_set_identity": (c_int, [ctx_p, c_void_p, c_void_p, c_int32]),
+        "nws_flags": (c_int, [ctx_p, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_float)]),
+        "nws_summary": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_float)]),
         "nwr_read_bam": (c_int, [c_char_p, c_void_p, c_int64, POINTER(c_void_p), c_char_p, c_int64]),
         "nwr_bam_free": (None, [c_void_p]),
         "nwr_bam_count": (c_int64, [c_void_p]),
@@ -403,7 +420,7 @@ def exported_symbols() -> dict:
     """Map of each declared symbol to whether the loaded library exports it."""
     lib = load()
     out = {}
-    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + COUNT_EXPORTS + DEMUX_EXPORTS + REGION_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + INGEST_EXPORTS + SYNTH_EXPORTS:
+    for name in EXPORTS + QUANT_EXPORTS + ALLELE_EXPORTS + COUNT_EXPORTS + DEMUX_EXPORTS + SUMMARY_EXPORTS + REGION_EXPORTS + FLASH_EXPORTS + TRIM_EXPORTS + FRONT_EXPORTS + INGEST_EXPORTS + SYNTH_EXPORTS:
         try:
             getattr(lib, name)
             out[name] = name not in _MISSING

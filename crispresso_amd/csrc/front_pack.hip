@@ -389,6 +389,15 @@ extern "C" int nwp_fetch(const nwp_result* res, uint8_t* status, int64_t* offset
     return 0;
 }
 
+int nw_front::view_prepared(const nwp_result* res, PreparedView* out) {
+    if (!res || !res->handle || !out) return NW_E_INVALID;
+    const nwp::Handle* h = (const nwp::Handle*)res->handle;
+    const bool any = res->m > 0;
+    *out = PreparedView{any ? h->text : nullptr, any ? h->quals : nullptr, h->offsets.data(), res->m, res->total,
+                        h->device, any ? h->b.e1 : nullptr};
+    return NW_OK;
+}
+
 namespace nwp {
 
 // What both entries check before they look at the reads: the arguments, the context's state, the

@@ -36,6 +36,8 @@
 //            group's first position (binary search of the exception list).
 // The reads are uploaded in chunks into one text buffer that stays resident for the gather, the
 // packer and, through nwd_adopt_group, the aligner (nw_front::set_packed_batch on a slice).
+// nwd_assign_prepared fills that buffer from the front end's merged text in HBM instead
+// (nw_front::view_prepared): the chunks' copies are device to device, nothing else differs.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -729,11 +731,14 @@ int nwd_set_amplicons(nwd_ctx* c, const uint8_t* refs, const int64_t* ref_offset
     return NW_OK;
 }
 
-int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t n, int32_t min_hits,
-               int32_t both_strands, int32_t* which, uint8_t* strand, int32_t* votes, int32_t* rival,
-               int64_t* counts, int64_t* n_assigned, int64_t* n_tie, int64_t* n_no_hit, float* kernel_ms) {
-    if (!c) return NW_E_INVALID;
-    if (c->k == 0) return fail(c, NW_E_STATE, "nwd_assign before nwd_set_amplicons");
+// nwd_assign and nwd_assign_prepared: `reads` is indexed by the caller's offsets and lies in host
+// memory, or (on_device) in this context's HBM, complete once `ready` (may be null) has passed.
+// The chunks' copies into the text buffer are then device to device, and a fallback read is
+// copied down from that buffer.
+static int assign_reads(nwd_ctx* c, const uint8_t* reads, bool on_device, hipEvent_t ready, const int64_t* offsets,
+                        int64_t n, int32_t min_hits, int32_t both_strands, int32_t* which, uint8_t* strand,
+                        int32_t* votes, int32_t* rival, int64_t* counts, int64_t* n_assigned, int64_t* n_tie,
+                        int64_t* n_no_hit, float* kernel_ms) {
     if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
     if (min_hits < 1) return fail(c, NW_E_UNSUPPORTED, "min_hits %d: at least 1", (int)min_hits);
     if (n > 0 && (!reads || !offsets)) return fail(c, NW_E_INVALID, "null input array");
@@ -788,6 +793,8 @@ int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t
         a.rival = c->d_rival.p;
         a.fb = c->d_fb.p;
         a.counters = c->d_counters.p;
+        if (on_device && ready) HIP_TRY(c, hipStreamWaitEvent(st, ready, 0));
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
         for (int64_t r0 = 0; r0 < n;) {
             int64_t r1;
             if (c->chunk_reads > 0) {
@@ -800,8 +807,7 @@ int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t
             const int64_t cn = r1 - r0, cbytes = offsets[r1] - offsets[r0];
             const auto t0 = std::chrono::steady_clock::now();
             if (cbytes > 0)
-                HIP_TRY(c, hipMemcpyAsync(c->d_text.p + (offsets[r0] - base), reads + offsets[r0], (size_t)cbytes,
-                                          hipMemcpyHostToDevice, st));
+                HIP_TRY(c, hipMemcpyAsync(c->d_text.p + (offsets[r0] - base), reads + offsets[r0], (size_t)cbytes, kind, st));
             HIP_TRY(c, hipStreamSynchronize(st));
             c->phase_ms[1] += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
             a.r0 = r0;
@@ -829,10 +835,17 @@ int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t
             std::vector<uint32_t> fb((size_t)nfb);
             HIP_TRY(c, hipMemcpy(fb.data(), a.fb, sizeof(uint32_t) * (size_t)nfb, hipMemcpyDeviceToHost));
             if (!c->host_index_built) build_host_index(c);
+            std::vector<uint8_t> one((size_t)NWD_MAX_READ);
             for (uint32_t r : fb) {
                 if ((int64_t)r >= n) return fail(c, NW_E_STATE, "inconsistent fallback read");
-                decide_on_host(c, reads + offsets[r], (int)(offsets[r + 1] - offsets[r]), min_hits, both,
-                               &c->which[r], &c->strand[r], &h_votes[r], &h_rival[r]);
+                const int len = (int)(offsets[r + 1] - offsets[r]);
+                const uint8_t* s = reads + offsets[r];
+                if (on_device) {      // the read copied down from the text buffer, one at a time
+                    if (len > 0)
+                        HIP_TRY(c, hipMemcpy(one.data(), c->d_text.p + (offsets[r] - base), (size_t)len, hipMemcpyDeviceToHost));
+                    s = one.data();
+                }
+                decide_on_host(c, s, len, min_hits, both, &c->which[r], &c->strand[r], &h_votes[r], &h_rival[r]);
             }
         }
         c->fallback = nfb;
@@ -864,6 +877,30 @@ int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t
     if (n_no_hit) *n_no_hit = nn;
     if (kernel_ms) *kernel_ms = c->phase_ms[0];
     return NW_OK;
+}
+
+int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t n, int32_t min_hits,
+               int32_t both_strands, int32_t* which, uint8_t* strand, int32_t* votes, int32_t* rival,
+               int64_t* counts, int64_t* n_assigned, int64_t* n_tie, int64_t* n_no_hit, float* kernel_ms) {
+    if (!c) return NW_E_INVALID;
+    if (c->k == 0) return fail(c, NW_E_STATE, "nwd_assign before nwd_set_amplicons");
+    return assign_reads(c, reads, false, nullptr, offsets, n, min_hits, both_strands, which, strand, votes, rival, counts,
+                        n_assigned, n_tie, n_no_hit, kernel_ms);
+}
+
+int nwd_assign_prepared(nwd_ctx* c, const nwp_result* res, int32_t min_hits, int32_t both_strands, int32_t* which,
+                        uint8_t* strand, int32_t* votes, int32_t* rival, int64_t* counts, int64_t* n_assigned,
+                        int64_t* n_tie, int64_t* n_no_hit, float* kernel_ms) {
+    if (!c) return NW_E_INVALID;
+    nw_front::PreparedView v{};
+    if (nw_front::view_prepared(res, &v) != NW_OK) return fail(c, NW_E_INVALID, "a null or released nwp_result");
+    if (c->k == 0) return fail(c, NW_E_STATE, "nwd_assign_prepared before nwd_set_amplicons");
+    if (v.device != c->device)
+        return fail(c, NW_E_INVALID, "the prepared reads lie on device %d, the index on device %d", v.device, c->device);
+    if (v.m < 0 || v.total < 0 || v.offsets[0] != 0 || v.offsets[v.m] != v.total)
+        return fail(c, NW_E_INVALID, "inconsistent nwp_result");
+    return assign_reads(c, v.text, true, v.ready, v.offsets, v.m, min_hits, both_strands, which, strand, votes, rival,
+                        counts, n_assigned, n_tie, n_no_hit, kernel_ms);
 }
 
 int nwd_gather(nwd_ctx* c, int64_t* group_offsets, int64_t* order, uint8_t* text, int64_t* text_offsets,

@@ -19,7 +19,9 @@
 // contributions to the block's LDS copy of the vectors -- once per distinct
 // position, which is what numpy's buffered `vec[idx] += 1` does -- and clears the
 // position array for the next read.  Blocks write their vectors to a partial
-// slab; a second kernel sums the slabs into int64 totals.
+// slab; a second kernel sums the slabs into int64 totals.  An amplicon whose vectors
+// and histograms do not fit in LDS beside the rest (from about 1,400 bases) takes
+// quant_kernel_long: the same body adding straight into the block's slab in HBM.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -96,11 +98,23 @@ struct Carry {
     int prev;               // gap state of the column before the step (bit0 read gap, bit1 amplicon gap)
 };
 
-__global__ __launch_bounds__(512) void quant_kernel(QArgs a) {
+// GT (an amplicon whose vectors, counters and histograms do not fit in LDS beside the rest): the
+// block accumulates straight into its slab of a.partial, which the host zeroed, with device
+// atomics; LDS then starts at the prefix tables (base_words leaves the slab's words out).  The
+// adds are integers, so the totals are the same either way.
+template <bool GT>
+__device__ __forceinline__ void quant_body(const QArgs& a) {
     extern __shared__ uint32_t smem[];
     const int LEN = a.LEN;
-    uint32_t* blk = smem;                                // vectors, counters, histograms
-    int32_t* incp = (int32_t*)(blk + a.nwords);
+    uint32_t* blk;                                       // vectors, counters, histograms
+    int32_t* incp;
+    if constexpr (GT) {
+        blk = a.partial + (int64_t)blockIdx.x * a.nwords;
+        incp = (int32_t*)smem;
+    } else {
+        blk = smem;
+        incp = (int32_t*)(blk + a.nwords);
+    }
     int32_t* exop = incp + (LEN + 1);
     int32_t* splp = exop + (LEN + 1);
     uint8_t* tbl = (uint8_t*)(splp + (LEN + 1));
@@ -111,7 +125,8 @@ __global__ __launch_bounds__(512) void quant_kernel(QArgs a) {
     run4* druns = (run4*)(posw + ((LEN + 1) & ~1));
     run4* iruns = druns + a.run_cap;
 
-    for (int i = threadIdx.x; i < a.nwords; i += blockDim.x) blk[i] = 0;
+    if constexpr (!GT)
+        for (int i = threadIdx.x; i < a.nwords; i += blockDim.x) blk[i] = 0;
     const int pref_words = 3 * (LEN + 1) + (LEN + 3) / 4;
     for (int i = threadIdx.x; i < pref_words; i += blockDim.x) incp[i] = a.prefix[i];
     for (int i = threadIdx.x; i < wpb * a.wave_words; i += blockDim.x) smem[a.base_words + i] = 0;
@@ -421,10 +436,15 @@ __global__ __launch_bounds__(512) void quant_kernel(QArgs a) {
         if (valid) a.out[idx] = myout;
     }
 
-    __syncthreads();
-    uint32_t* dst = a.partial + (int64_t)blockIdx.x * a.nwords;
-    for (int i = threadIdx.x; i < a.nwords; i += blockDim.x) dst[i] = blk[i];
+    if constexpr (!GT) {
+        __syncthreads();
+        uint32_t* dst = a.partial + (int64_t)blockIdx.x * a.nwords;
+        for (int i = threadIdx.x; i < a.nwords; i += blockDim.x) dst[i] = blk[i];
+    }
 }
+
+__global__ __launch_bounds__(512) void quant_kernel(QArgs a) { quant_body<false>(a); }
+__global__ __launch_bounds__(512) void quant_kernel_long(QArgs a) { quant_body<true>(a); }
 
 // Sum of the per-block slabs: blockIdx.y takes a contiguous slice of the slabs,
 // adds into the (zeroed) int64 totals.
@@ -970,6 +990,7 @@ int64_t words_for(int32_t LEN, int64_t stride) { return (int64_t)nwq::NV * LEN +
 
 struct QGeom {
     int wpb, grid, lds, run_cap, wave_words, base_words, nwords;
+    bool gtot;      // the totals in HBM, not in LDS
 };
 
 int geometry(nwq_ctx* c, int64_t stride, int64_t n, QGeom* g) {
@@ -989,11 +1010,25 @@ int geometry(nwq_ctx* c, int64_t stride, int64_t n, QGeom* g) {
             break;
         }
     }
+    g->gtot = false;
+    if (!g->wpb) {   // a long amplicon: the totals stay in the block's slab in HBM (quant_kernel_long)
+        g->gtot = true;
+        g->base_words = (pref_words + 1) & ~1;
+        for (int w : {8, 4, 2, 1}) {
+            const int lds = 4 * (g->base_words + w * g->wave_words);
+            if (lds <= kMaxLds / 2 || (w == 1 && lds <= kMaxLds)) {
+                g->wpb = w;
+                g->lds = lds;
+                break;
+            }
+        }
+    }
     if (!g->wpb)
         return fail(c, NW_E_UNSUPPORTED, "quantification state for amplicon length %d / stride %lld exceeds LDS",
                     LEN, (long long)stride);
     int per_cu = 0;
-    HIP_TRY(c, (hipError_t)occupancy(c, (const void*)nwq::quant_kernel, 64 * g->wpb, g->lds, &per_cu));
+    const void* kernel = g->gtot ? (const void*)nwq::quant_kernel_long : (const void*)nwq::quant_kernel;
+    HIP_TRY(c, (hipError_t)occupancy(c, kernel, 64 * g->wpb, g->lds, &per_cu));
     per_cu = std::max(per_cu, 1);
     const int64_t need = (n + g->wpb - 1) / g->wpb;
     g->grid = (int)std::max<int64_t>(1, std::min<int64_t>(need, (int64_t)c->num_cus * per_cu));
@@ -1038,7 +1073,12 @@ int run_impl(nwq_ctx* c, uint8_t* d_aln, int64_t stride, const int32_t* d_len, i
     a.base_words = g.base_words;
     a.flags = c->flags;
     if (!started) HIP_TRY(c, hipEventRecord(c->ev0, c->stream));   // (the row expansion records it first)
-    hipLaunchKernelGGL(nwq::quant_kernel, dim3(g.grid), dim3(64 * g.wpb), g.lds, c->stream, a);
+    if (g.gtot) {
+        HIP_TRY(c, hipMemsetAsync(a.partial, 0, sizeof(uint32_t) * (size_t)g.grid * g.nwords, c->stream));
+        hipLaunchKernelGGL(nwq::quant_kernel_long, dim3(g.grid), dim3(64 * g.wpb), g.lds, c->stream, a);
+    } else {
+        hipLaunchKernelGGL(nwq::quant_kernel, dim3(g.grid), dim3(64 * g.wpb), g.lds, c->stream, a);
+    }
     HIP_TRY(c, hipGetLastError());
     const int nslabs = slabs0 + g.grid;
     const int slices = std::min(nslabs, 32), slice = (nslabs + slices - 1) / slices;

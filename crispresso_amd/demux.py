@@ -12,9 +12,13 @@ as no hit, not guessed.
 * :func:`align_demultiplexed` -- the same, then :func:`crispresso_amd.pooled.align_pooled`
 * :func:`align_demultiplexed_resident` -- assigned, grouped and 2-bit packed in HBM, each group
   adopted by the aligner where it lies; only decisions, records and runs cross PCIe
+* :func:`summarize_pooled` -- raw reads (host, or merged pairs resident in HBM) to the reference's
+  ``SAMPLES_QUANTIFICATION_SUMMARY.txt``: the identity filter and the counts on the device
+  (``include/crispr_summary.h``, crispresso_amd/csrc/nw_summary.hip), 16 integers back per amplicon
 * :func:`read_amplicons_file` -- the reference's tab-separated amplicon table
-* ``python -m crispresso_amd.demux`` -- FASTQ + amplicon table -> per-amplicon FASTQ files and
-  the reference's ``REPORT_READS_ALIGNED_TO_AMPLICONS.txt``
+* ``python -m crispresso_amd.demux`` -- FASTQ (``-r2``: pairs) + amplicon table -> per-amplicon
+  FASTQ files, the reference's ``REPORT_READS_ALIGNED_TO_AMPLICONS.txt`` and, with ``--summary``,
+  the summary table
 
 Every refusal is made here, before any GPU call.  There is no CPU fallback.
 """
@@ -209,6 +213,23 @@ class GpuDemultiplexer:
                                          ctypes.byref(ms)), "nwd_assign")
         return which, strand, votes, rival, counts, int(na.value), int(nt.value), int(nn.value), float(ms.value)
 
+    def assign_prepared(self, rr, min_hits: int, both_strands: bool):
+        """:meth:`assign` on the merged reads a front-end call left in HBM (``rr``: a
+        :class:`crispresso_amd.frontend.ResidentReads`; ``nwd_assign_prepared``): no upload, the
+        same return.  ``rr`` may be closed right after."""
+        n = len(rr)
+        which, strand = np.empty(n, np.int32), np.empty(n, np.uint8)
+        votes, rival = np.empty(n, np.int32), np.empty(n, np.int32)
+        counts = np.zeros(self.n_amplicons, np.int64)
+        na, nt, nn = (ctypes.c_int64() for _ in range(3))
+        ms = ctypes.c_float()
+        self._packed = None
+        self._check(self._lib.nwd_assign_prepared(self._ctx, ctypes.byref(rr.result()), min_hits, int(bool(both_strands)),
+                                                  _lib.ptr(which), _lib.ptr(strand), _lib.ptr(votes), _lib.ptr(rival),
+                                                  _lib.ptr(counts), ctypes.byref(na), ctypes.byref(nt),
+                                                  ctypes.byref(nn), ctypes.byref(ms)), "nwd_assign_prepared")
+        return which, strand, votes, rival, counts, int(na.value), int(nt.value), int(nn.value), float(ms.value)
+
     def gather(self, n_assigned: int, text_cap: int):
         """(group_offsets, order, text, text_offsets) of the last :meth:`assign`; a short
         ``text_cap`` is answered with the needed size, and the call is made again."""
@@ -370,6 +391,319 @@ def align_demultiplexed_resident(amplicons: Sequence[str], reads, aligner, *, mi
     return batches, res, skipped
 
 
+# ---- raw reads to the per-amplicon summary ------------------------------------------------------
+
+SUMMARY_COLUMNS = ("Name", "Unmodified%", "NHEJ%", "HDR%", "Mixed_HDR-NHEJ%", "Reads_aligned", "Reads_total")
+MAX_QUANT_AMPLICON = 32768          # nwq_params.len_amplicon must stay below it
+
+
+class SummaryError(RuntimeError):
+    """A failed nws_* call; ``code`` is its return, ``n_out_of_range`` what nws_flags counted."""
+
+    def __init__(self, msg: str, code: int, n_out_of_range: int = 0):
+        super().__init__(msg)
+        self.code, self.n_out_of_range = code, n_out_of_range
+
+
+def _first_at_least(L: int, bound, strict: bool) -> int:
+    """The smallest i in [0, L] with printed_percent(i, L) > bound (strict) or >= bound; L + 1 if
+    none.  The printed value does not decrease with i: a bisection."""
+    from .aligner import printed_percent
+
+    def ok(i: int) -> bool:
+        v = printed_percent(i, L)
+        return v > bound if strict else v >= bound
+
+    if not ok(L):
+        return L + 1
+    lo, hi = 0, L                   # ok(hi); the answer lies in [lo, hi]
+    while lo < hi:
+        mid = (lo + hi) >> 1
+        if ok(mid):
+            hi = mid
+        else:
+            lo = mid + 1
+    return lo
+
+
+def identity_thresholds(min_identity_score: float, max_cols: int, start: int = 0) -> Tuple[np.ndarray, np.ndarray]:
+    """The tables ``nws_set_identity`` takes, int32 ``[max_cols + 1]`` indexed by the alignment
+    length L (entries below ``start`` are left 0, for a caller that extends its tables):
+
+    * ``keep_min[L]``: the smallest ``n_ident`` whose printed identity
+      ``float("%.1f" % (100.0 * n_ident / L))`` is strictly greater than ``min_identity_score``
+      (the reference's filter, CRISPRessoCORE.py:1997-2012), ``L + 1`` if none is;
+    * ``unmod_min[L]``: the smallest ``n_ident`` that prints ``100.0`` (UNMODIFIED, CORE:2014).
+
+    The reference compares what it printed, not the ratio: 150/250 prints 60.0 and is dropped
+    at 60, and from L = 2000 on a read with one mismatch prints 100.0."""
+    max_cols = int(max_cols)
+    if max_cols < 0:
+        raise ValueError("max_cols must not be negative")
+    keep_min, unmod_min = np.zeros(max_cols + 1, np.int32), np.zeros(max_cols + 1, np.int32)
+    bound = float(min_identity_score)
+    for L in range(max(int(start), 0), max_cols + 1):
+        keep_min[L] = _first_at_least(L, bound, True)
+        unmod_min[L] = _first_at_least(L, 100.0, False)
+    return keep_min, unmod_min
+
+
+class GpuSummarizer:
+    """One ``nws_ctx`` (one GPU): the flags and the 16 counters of a resident group
+    (``include/crispr_summary.h``).  Not thread-safe."""
+
+    def __init__(self, device: int = 0):
+        self._lib = _lib.load()
+        ctx = ctypes.c_void_p()
+        rc = self._lib.nws_create(int(device), ctypes.byref(ctx))
+        if rc != 0:
+            raise NativeLibraryError(f"nws_create(device={device}) failed with code {rc} (no GPU?)")
+        self._ctx = ctx
+        self.device = device
+        self.min_identity_score: Optional[float] = None
+        self.keep_min = self.unmod_min = np.zeros(0, np.int32)
+        self.flags_ms = self.summary_ms = 0.0
+
+    def close(self) -> None:
+        if getattr(self, "_ctx", None):
+            self._lib.nws_destroy(self._ctx)
+            self._ctx = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _check(self, rc: int, what: str, bad: int = 0) -> None:
+        if rc != 0:
+            msg = self._lib.nws_last_error(self._ctx).decode(errors="replace")
+            raise SummaryError(f"{what} failed ({rc}): {msg}", rc, bad)
+
+    def set_identity(self, keep_min: np.ndarray, unmod_min: np.ndarray) -> None:
+        keep_min = np.ascontiguousarray(keep_min, np.int32)
+        unmod_min = np.ascontiguousarray(unmod_min, np.int32)
+        if keep_min.ndim != 1 or keep_min.shape != unmod_min.shape or len(keep_min) < 1:
+            raise ValueError("the two tables must hold max_cols + 1 values each")
+        self._check(self._lib.nws_set_identity(self._ctx, _lib.ptr(keep_min), _lib.ptr(unmod_min), len(keep_min) - 1),
+                    "nws_set_identity")
+        self.keep_min, self.unmod_min = keep_min, unmod_min
+
+    def ensure_identity(self, min_identity_score: float, max_cols: int) -> None:
+        """Tables for ``min_identity_score`` that reach ``max_cols``: built once, extended when a
+        later group's alignments are longer."""
+        score = float(min_identity_score)
+        have = len(self.keep_min) - 1 if self.min_identity_score == score else -1
+        if have >= max_cols:
+            return
+        keep_min, unmod_min = identity_thresholds(score, max_cols, have + 1)
+        keep_min[:have + 1], unmod_min[:have + 1] = self.keep_min[:have + 1], self.unmod_min[:have + 1]
+        self.min_identity_score = None
+        self.set_identity(keep_min, unmod_min)
+        self.min_identity_score = score
+
+    def flags(self, d_stats: int, n: int, d_pre: int, d_keep: int) -> None:
+        """``nws_flags``: device pointers (ints) of n nw_stat records in, pre and keep (uint8 [n])
+        out.  A record outside the tables raises :class:`SummaryError` with their number."""
+        bad, ms = ctypes.c_int64(), ctypes.c_float()
+        rc = self._lib.nws_flags(self._ctx, d_stats, n, d_pre, d_keep, ctypes.byref(bad), ctypes.byref(ms))
+        self.flags_ms = float(ms.value)
+        self._check(rc, "nws_flags", int(bad.value))
+
+    def summary(self, d_reads: int, d_pre: int, d_keep: int, n: int) -> np.ndarray:
+        """``nws_summary``: the 16 slots (int64) of n nwq_read records on the device."""
+        out = np.zeros(_lib.NWS_SLOTS, np.int64)
+        ms = ctypes.c_float()
+        rc = self._lib.nws_summary(self._ctx, d_reads, d_pre, d_keep, n, _lib.ptr(out), ctypes.byref(ms))
+        self.summary_ms = float(ms.value)
+        self._check(rc, "nws_summary")
+        return out
+
+
+_DEFAULT_SUMMARIZER: Dict[int, GpuSummarizer] = {}
+
+
+def default_summarizer(device: int = 0) -> GpuSummarizer:
+    s = _DEFAULT_SUMMARIZER.get(device)
+    if s is None:
+        s = _DEFAULT_SUMMARIZER[device] = GpuSummarizer(device)
+    return s
+
+
+@dataclass
+class PooledSummary:
+    """One :func:`summarize_pooled` call."""
+
+    counts: np.ndarray                 # int64 [amplicons, 16]: nws_summary's slots, zeros for a skipped amplicon
+    frame: "object"                    # pandas.DataFrame: SAMPLES_QUANTIFICATION_SUMMARY.txt's rows
+    result: DemuxResult
+    skipped: List[int]
+    kernel_ms: Dict[str, float]        # device ms of the flags and summary kernels, summed over the groups
+
+
+def summary_frame(names: Sequence[str], counts: np.ndarray, n_reads: Sequence[int], skipped: Sequence[int]):
+    """The table of CRISPRessoPooledCORE.py:1382-1413 from the 16 slots per amplicon: the shares
+    of N_TOTAL (a float, as the reference parses it) times 100, NaN throughout for an amplicon
+    that was skipped or has no read aligned (the reference finds no quantification file)."""
+    import pandas as pd
+
+    rows = []
+    skipped = set(int(g) for g in skipped)
+    for g, name in enumerate(names):
+        c = counts[g]
+        N_TOTAL = float(c[1])
+        if g in skipped or N_TOTAL == 0:
+            rows.append([name, np.nan, np.nan, np.nan, np.nan, np.nan, int(n_reads[g])])
+            continue
+        N_UNMODIFIED, N_MODIFIED, N_REPAIRED, N_MIXED_HDR_NHEJ = (float(c[s]) for s in (2, 3, 4, 5))
+        rows.append([name, N_UNMODIFIED / N_TOTAL * 100., N_MODIFIED / N_TOTAL * 100., N_REPAIRED / N_TOTAL * 100.,
+                     N_MIXED_HDR_NHEJ / N_TOTAL * 100., N_TOTAL, int(n_reads[g])])
+    return pd.DataFrame(rows, columns=list(SUMMARY_COLUMNS))
+
+
+def write_summary(path: str, frame) -> None:
+    """SAMPLES_QUANTIFICATION_SUMMARY.txt as the reference writes it (POOLED:1414-1416)."""
+    frame.fillna("NA").to_csv(path, sep="\t", index=None)
+
+
+def check_summary_rows(rows: Sequence[dict]) -> List[str]:
+    """The refusals :func:`summarize_pooled` makes on the amplicon table, before any GPU call;
+    returns the amplicon sequences."""
+    for row in rows:
+        if row.get("Expected_HDR"):
+            raise ValueError(f"amplicon {row['Name']}: Expected_HDR is given, and dual alignment per amplicon is not built")
+        if len(row["Amplicon_Sequence"]) >= MAX_QUANT_AMPLICON:
+            raise ValueError(f"amplicon {row['Name']} has {len(row['Amplicon_Sequence'])} bases: fewer than "
+                             f"{MAX_QUANT_AMPLICON} are supported")
+    return [row["Amplicon_Sequence"] for row in rows]
+
+
+def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1000, min_identity_score: float = 60.0,
+                     window_around_sgrna: int = 1, cleavage_offset: int = -3, exclude_bp_from_left: int = 15,
+                     exclude_bp_from_right: int = 15, ignore_substitutions: bool = False,
+                     ignore_insertions: bool = False, ignore_deletions: bool = False,
+                     hide_mutations_outside_window_NHEJ: bool = False, k: int = 16, min_hits: int = 2,
+                     both_strands: bool = True, on_group=None, demultiplexer: Optional[GpuDemultiplexer] = None,
+                     quantifier=None, summarizer: Optional[GpuSummarizer] = None) -> PooledSummary:
+    """Raw reads to CRISPRessoPooled's SAMPLES_QUANTIFICATION_SUMMARY.txt (amplicon mode) with the
+    reads in HBM from the first kernel to the last.
+
+    ``rows``: what :func:`read_amplicons_file` returns.  ``reads``: the packed host pair
+    ``(buf, offsets)`` (or a list of ``str``), uploaded once, or a
+    :class:`crispresso_amd.frontend.ResidentReads`, the merged pairs a front-end call left in
+    HBM (assigned there, ``nwd_assign_prepared``).  ``aligner`` must be on the reads' device.
+
+    The reads are assigned, oriented, grouped and packed as by
+    :func:`align_demultiplexed_resident`.  Then, for every amplicon with strictly more than
+    ``min_reads`` reads, in index order: ``set_reference``, adoption, one pass; ``nws_flags`` on
+    the records (the filter on the printed identity against ``min_identity_score`` and the
+    UNMODIFIED flag, from :func:`identity_thresholds`); the quantifier on the resident ops with
+    that device ``pre`` (its globals from the row's sgRNA and coding sequence,
+    :func:`crispresso_amd.quantify.globals_from_args`); ``nws_summary``; ``on_group(g, aligner,
+    n)`` while the group is resident.  Per group only 16 integers come back.
+
+    Differences from the reference, deliberate: a read is aligned in the orientation the
+    demultiplexer chose and is not retried reverse-complemented; an ``Expected_HDR`` row is
+    refused; the quantifier's effect vectors and histograms (not returned here) are not masked
+    by the identity filter.  A kept read that is not an alignment of its amplicon (slot 15)
+    raises :class:`crispresso_amd.quantify.QuantificationError`."""
+    import types
+
+    from . import quantify
+    from .devmem import DeviceBuffer
+    from .frontend import ResidentReads
+
+    k, min_hits = check_params(k, min_hits)
+    amplicons = check_summary_rows(rows)
+    abuf, aoff = pack_amplicons(amplicons)
+    device = int(getattr(aligner, "device", 0))
+    resident = isinstance(reads, ResidentReads)
+    if resident:
+        if reads.closed:
+            raise ValueError("the resident reads were released")
+        if int(reads.device) != device:
+            raise ValueError(f"the aligner is on device {device}, the resident reads on device {reads.device}")
+    else:
+        rbuf, roff = _packed(reads)
+        check_offsets(rbuf, roff, "reads", MAX_READ)
+        if len(roff) - 1 > 2 ** 31 - 1:
+            raise ValueError("more than 2^31 - 1 reads")
+    for what, stage in (("demultiplexer", demultiplexer), ("quantifier", quantifier), ("summarizer", summarizer)):
+        if stage is not None and int(stage.device) != device:
+            raise ValueError(f"the aligner is on device {device}, the {what} on device {stage.device}")
+    d = demultiplexer or default_demultiplexer(device)
+    q = quantifier or quantify.default_quantifier(device)
+    s = summarizer or default_summarizer(device)
+
+    n_windows, n_ambiguous = d.set_amplicons(abuf, aoff, k)
+    if resident:
+        which, strand, votes, rival, counts, na, nt, nn, ms = d.assign_prepared(reads, min_hits, both_strands)
+    else:
+        which, strand, votes, rival, counts, na, nt, nn, ms = d.assign(rbuf, roff, min_hits, both_strands)
+    pk = d.pack(na)
+    res = DemuxResult(which, strand, votes, rival, counts, pk.group_offsets, pk.order, np.zeros(0, np.uint8),
+                      pk.text_offsets, n_windows, n_ambiguous, nt, nn, d.last_fallback(), ms,
+                      d.phase_times()["upload_wall"])
+    min_reads = max(int(min_reads), 0)      # (an amplicon without a read has nothing to adopt)
+    keep = [g for g in range(len(amplicons)) if int(counts[g]) > min_reads]
+    skipped = [g for g in range(len(amplicons)) if int(counts[g]) <= min_reads]
+    out = np.zeros((len(amplicons), _lib.NWS_SLOTS), np.int64)
+    times = {"flags": 0.0, "summary": 0.0, "quantify": 0.0}
+    most = max((int(counts[g]) for g in keep), default=0)
+    mode = getattr(aligner, "output_mode", "rows")
+    saved_globals = quantify._GLOBALS
+    aligner.set_output("ops")
+    try:
+        with DeviceBuffer(most, device) as d_pre, DeviceBuffer(most, device) as d_keep, \
+                DeviceBuffer(16 * most, device) as d_out:
+            for g in keep:
+                amp, row = amplicons[g], rows[g]
+                aligner.set_reference(amp)
+                n = d.adopt(aligner, g)
+                aligner.run_async()
+                aligner.sync()
+                dev = aligner.device_ops()
+                s.ensure_identity(min_identity_score, int(dev["max_cols"]))
+                try:
+                    s.flags(dev["stats"], n, d_pre.ptr, d_keep.ptr)
+                except SummaryError as exc:
+                    raise SummaryError(f"amplicon {row['Name']}: {exc}", exc.code, exc.n_out_of_range) from None
+                args = types.SimpleNamespace(
+                    amplicon_seq=amp, guide_seq=row.get("sgRNA") or None, coding_seq=row.get("Coding_sequence") or None,
+                    cleavage_offset=cleavage_offset, window_around_sgrna=window_around_sgrna,
+                    exclude_bp_from_left=exclude_bp_from_left, exclude_bp_from_right=exclude_bp_from_right,
+                    ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
+                    ignore_deletions=ignore_deletions,
+                    hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ,
+                    expected_hdr_amplicon_seq=None)
+                try:
+                    q.set_params(quantify.globals_from_args(args), args, amplicon_has_n="N" in amp.upper())
+                    q.run_device_ops(amp, dev, d_pre.ptr, n, d_out.ptr)
+                except quantify.QuantificationError as exc:     # (e.g. an amplicon too long for the quantifier's LDS)
+                    raise quantify.QuantificationError(f"amplicon {row['Name']}: {exc}") from None
+                times["quantify"] += q.last_kernel_ms
+                out[g] = s.summary(d_out.ptr, d_pre.ptr, d_keep.ptr, n)
+                times["flags"] += s.flags_ms
+                times["summary"] += s.summary_ms
+                if int(out[g, 15]):
+                    raise quantify.QuantificationError(
+                        f"amplicon {row['Name']}: {int(out[g, 15])} kept reads are not alignments of it "
+                        "(LEN_AMPLICON bases)")
+                if on_group is not None:
+                    on_group(g, aligner, n)
+    finally:
+        quantify._GLOBALS = saved_globals
+        aligner.set_output(mode)
+    frame = summary_frame([row["Name"] for row in rows], out, counts.tolist(), skipped)
+    return PooledSummary(out, frame, res, skipped, times)
+
+
 # ---- the command line's files ------------------------------------------------------------------
 
 def clean_filename(name: str) -> str:
@@ -446,15 +780,60 @@ def unassigned_report_lines(n_reads: int, n_tie: int, n_no_hit: int) -> List[str
     return out
 
 
+def _resident_fastq(rows, fastq, fastq_r2, device, k, min_hits, both_strands, min_reads, front, summary):
+    """The front end's way through the files: parsed, filtered, trimmed and merged on the GPU
+    (``frontend.prepare_fastq_resident``), assigned where the merged reads lie, and with
+    ``summary`` (the options of :func:`summarize_pooled`) quantified there.  Returns (header
+    lines, sequences, qualities, DemuxResult, PooledSummary or None)."""
+    from .aligner import GpuAligner
+    from .frontend import prepare_fastq_resident
+
+    amplicons = check_summary_rows(rows) if summary is not None else [r["Amplicon_Sequence"] for r in rows]
+    with GpuAligner(device) as al:
+        al.set_reference(amplicons[0])          # the front end wants one; any amplicon will do
+        rr, _ = prepare_fastq_resident(al, fastq, fastq_r2, with_quals=True, **front)
+        with rr:
+            text, qual, off = rr.fetch_text(), rr.fetch_quals(), rr.offsets.tolist()
+            seqs = [text[off[j]:off[j + 1]].tobytes() for j in range(len(rr))]
+            quals = [qual[off[j]:off[j + 1]].tobytes() for j in range(len(rr))]
+            if summary is not None:
+                ps = summarize_pooled(rows, rr, al, min_reads=min_reads, k=k, min_hits=min_hits,
+                                      both_strands=both_strands, **summary)
+                return rr.headers, seqs, quals, ps.result, ps
+            k, min_hits = check_params(k, min_hits)
+            d = default_demultiplexer(device)
+            n_windows, n_ambiguous = d.set_amplicons(*pack_amplicons(amplicons), k)
+            which, strand, votes, rival, counts, na, nt, nn, ms = d.assign_prepared(rr, min_hits, both_strands)
+            pk = d.pack(na)
+            res = DemuxResult(which, strand, votes, rival, counts, pk.group_offsets, pk.order, np.zeros(0, np.uint8),
+                              pk.text_offsets, n_windows, n_ambiguous, nt, nn, d.last_fallback(), ms,
+                              d.phase_times()["upload_wall"])
+            return rr.headers, seqs, quals, res, None
+
+
 def demultiplex_fastq(amplicons_file: str, fastq: str, out_dir: str, *, k: int = 16, min_hits: int = 2,
-                      both_strands: bool = True, min_reads_to_use_region: int = 1000, device: int = 0) -> dict:
-    """The command line's work; returns what it wrote."""
+                      both_strands: bool = True, min_reads_to_use_region: int = 1000, device: int = 0,
+                      fastq_r2: Optional[str] = None, front: Optional[dict] = None,
+                      summary: Optional[dict] = None) -> dict:
+    """The command line's work; returns what it wrote.
+
+    With ``fastq_r2``, ``front`` (keyword arguments of ``frontend.prepare_fastq_resident``: the
+    quality filter, the trim program, the FLASH options) or ``summary`` (keyword arguments of
+    :func:`summarize_pooled`, ``{}`` for its defaults) the files go through the GPU front end:
+    the per-amplicon FASTQ files then hold the merged (filtered, trimmed) reads under R1's
+    headers with FLASH's ``/1`` cut, and with ``summary`` SAMPLES_QUANTIFICATION_SUMMARY.txt is
+    written as well."""
     from . import ingest
 
     rows = read_amplicons_file(amplicons_file)
-    names, seqs, quals = ingest.read_fastq(fastq, device)
-    res = demultiplex([r["Amplicon_Sequence"] for r in rows], [bytes(s) for s in seqs], k=k, min_hits=min_hits,
-                      both_strands=both_strands)
+    ps = None
+    if fastq_r2 is not None or front or summary is not None:
+        names, seqs, quals, res, ps = _resident_fastq(rows, fastq, fastq_r2, device, k, min_hits, both_strands,
+                                                      min_reads_to_use_region, front or {}, summary)
+    else:
+        names, seqs, quals = ingest.read_fastq(fastq, device)
+        res = demultiplex([r["Amplicon_Sequence"] for r in rows], [bytes(s) for s in seqs], k=k, min_hits=min_hits,
+                          both_strands=both_strands)
     os.makedirs(out_dir, exist_ok=True)
     files = []
     for g, row in enumerate(rows):
@@ -474,11 +853,16 @@ def demultiplex_fastq(amplicons_file: str, fastq: str, out_dir: str, *, k: int =
     with open(unassigned_report, "w") as f:
         f.write("\n".join(unassigned_report_lines(len(seqs), res.n_tie, res.n_no_hit)) + "\n")
     used = [g for g in range(len(rows)) if int(res.counts[g]) > min_reads_to_use_region]
-    return {"result": res, "rows": rows, "files": files, "unassigned": unassigned, "report": report,
-            "unassigned_report": unassigned_report, "regions_to_use": used, "n_reads": len(seqs)}
+    out = {"result": res, "rows": rows, "files": files, "unassigned": unassigned, "report": report,
+           "unassigned_report": unassigned_report, "regions_to_use": used, "n_reads": len(seqs)}
+    if ps is not None:
+        out["summary"] = ps
+        out["summary_file"] = os.path.join(out_dir, "SAMPLES_QUANTIFICATION_SUMMARY.txt")
+        write_summary(out["summary_file"], ps.frame)
+    return out
 
 
-def main(argv=None) -> int:
+def build_parser():
     import argparse
 
     p = argparse.ArgumentParser(prog="python -m crispresso_amd.demux",
@@ -493,16 +877,80 @@ def main(argv=None) -> int:
     p.add_argument("--forward_only", action="store_true", help="do not try the reads' reverse complement")
     p.add_argument("--min_reads_to_use_region", type=float, default=1000,
                    help="an amplicon is worth a CRISPResso run with more reads than this")
+    g = p.add_argument_group("the GPU front end (any of these sends the files through it)")
+    g.add_argument("-r2", "--fastq_r2", default=None, help="second mates: the pairs are merged as by FLASH")
+    g.add_argument("--trim_sequences", action="store_true", help="trim by --trimmomatic_options_string")
+    g.add_argument("--trimmomatic_options_string", default="",
+                   help="Trimmomatic steps, e.g. 'ILLUMINACLIP:adapters.fa:0:90:10:0:true MINLEN:40'")
+    g.add_argument("--min_paired_end_reads_overlap", type=int, default=4)
+    g.add_argument("--max_paired_end_reads_overlap", type=int, default=100)
+    g.add_argument("-q", "--min_average_read_quality", type=int, default=0)
+    g.add_argument("-s", "--min_single_bp_quality", type=int, default=0)
+    g = p.add_argument_group("the per-amplicon summary")
+    g.add_argument("--summary", action="store_true",
+                   help="align and quantify every amplicon's reads and write SAMPLES_QUANTIFICATION_SUMMARY.txt")
+    g.add_argument("--min_identity_score", type=float, default=60.0)
+    g.add_argument("--window_around_sgrna", type=int, default=1)
+    g.add_argument("--cleavage_offset", type=int, default=-3)
+    return p
+
+
+def options_from_args(p, args) -> dict:
+    """The keyword arguments of :func:`demultiplex_fastq` an argument set stands for.  Without any
+    of the front end's or the summary's options: exactly the arguments of the demultiplexing
+    alone (no ``fastq_r2``, ``front`` or ``summary``)."""
+    kw = dict(k=args.k, min_hits=args.min_hits, both_strands=not args.forward_only,
+              min_reads_to_use_region=args.min_reads_to_use_region)
+    front: dict = {}
+    if args.trim_sequences:
+        if not args.trimmomatic_options_string.strip():
+            p.error("--trim_sequences needs --trimmomatic_options_string (no adapter file is bundled)")
+        front["trim"] = args.trimmomatic_options_string
+    elif args.trimmomatic_options_string.strip():
+        p.error("--trimmomatic_options_string is used only with --trim_sequences")
+    if args.min_average_read_quality > 0:
+        front["min_bp_quality"] = args.min_average_read_quality
+    if args.min_single_bp_quality > 0:
+        front["min_single_bp_quality"] = args.min_single_bp_quality
+    overlap = (args.min_paired_end_reads_overlap, args.max_paired_end_reads_overlap)
+    if overlap != (4, 100):
+        if args.fastq_r2 is None:
+            p.error("the paired-end overlap options need -r2")
+        from .flash import FlashOptions
+
+        front["flash"] = FlashOptions(min_overlap=overlap[0], max_overlap=overlap[1])
+    if args.fastq_r2 is not None:
+        kw["fastq_r2"] = args.fastq_r2
+    if front:
+        kw["front"] = front
+    if args.summary:
+        kw["summary"] = dict(min_identity_score=args.min_identity_score, window_around_sgrna=args.window_around_sgrna,
+                             cleavage_offset=args.cleavage_offset)
+    elif (args.min_identity_score, args.window_around_sgrna, args.cleavage_offset) != (60.0, 1, -3):
+        p.error("--min_identity_score, --window_around_sgrna and --cleavage_offset are used only with --summary")
+    return kw
+
+
+def main(argv=None) -> int:
+    p = build_parser()
     args = p.parse_args(argv)
-    for f in (args.amplicons_file, args.fastq_r1):
+    files = [args.amplicons_file, args.fastq_r1] + ([args.fastq_r2] if args.fastq_r2 is not None else [])
+    for f in files:
         if not os.path.exists(f):
             p.error(f"cannot open {f}")
-    out = demultiplex_fastq(args.amplicons_file, args.fastq_r1, args.output_folder, k=args.k, min_hits=args.min_hits,
-                            both_strands=not args.forward_only, min_reads_to_use_region=args.min_reads_to_use_region)
+    kw = options_from_args(p, args)
+    if "summary" in kw:
+        try:
+            check_summary_rows(read_amplicons_file(args.amplicons_file))
+        except ValueError as exc:
+            p.error(str(exc))
+    out = demultiplex_fastq(args.amplicons_file, args.fastq_r1, args.output_folder, **kw)
     res = out["result"]
     print(f"{out['n_reads']} reads: {res.n_assigned} assigned to {len(out['rows'])} amplicons, {res.n_tie} ties, "
           f"{res.n_no_hit} without a hit; {len(out['regions_to_use'])} amplicons with more than "
           f"{args.min_reads_to_use_region:g} reads: {out['report']}")
+    if "summary_file" in out:
+        print(f"summary of {len(out['rows']) - len(out['summary'].skipped)} amplicons: {out['summary_file']}")
     return 0
 
 

@@ -11,7 +11,10 @@ with the clip, steps and merge kernels of :mod:`crispresso_amd.trim` and
 between.  The host receives each input read's status, the batch's text, offsets, lengths and
 source indices.  :func:`prepare_fastq` is that call on FASTQ files read by the interpreter;
 :func:`prepare_fastq_device` parses the files on the GPU (:mod:`crispresso_amd.ingest`) and hands
-the records to the same kernels where they lie (``nwp_prepare_records``).  There is no CPU
+the records to the same kernels where they lie (``nwp_prepare_records``).
+:func:`prepare_packed_resident` / :func:`prepare_fastq_resident` are the same calls with the merged
+reads kept in HBM (:class:`ResidentReads`) for a stage that reads them there
+(``demux.GpuDemultiplexer.assign_prepared``, ``demux.summarize_pooled``).  There is no CPU
 fallback: without the library or a GPU every call raises
 :class:`crispresso_amd._lib.NativeLibraryError`.
 """
@@ -78,13 +81,21 @@ def prepare_packed(aligner: GpuAligner, s1: np.ndarray, q1: np.ndarray, off1: np
     a reference; its output mode is set to "ops" unless ``force_ops_output`` is False (then a
     context in rows mode is refused, as by ``upload_packed``'s C entry).  When no read survives the
     context keeps its previous batch."""
+    lib, res, n = _call_packed("prepare_packed", aligner, s1, q1, off1, s2, q2, off2, min_bp_quality,
+                               min_single_bp_quality, trim, flash, with_quals, force_ops_output)
+    return _collect(aligner, lib, res, n, with_quals, with_packed)
+
+
+def _call_packed(who: str, aligner: GpuAligner, s1, q1, off1, s2, q2, off2, min_bp_quality, min_single_bp_quality, trim,
+                 flash, with_quals: bool, force_ops_output: bool):
+    """nwp_prepare on packed host reads: ``(lib, the live nwp_result, n)``."""
     paired = s2 is not None
-    prog = _program("prepare_packed", trim)
-    s1, q1, off1, s2, q2, off2 = _check_packed("prepare_packed", s1, q1, off1, s2, q2, off2)
+    prog = _program(who, trim)
+    s1, q1, off1, s2, q2, off2 = _check_packed(who, s1, q1, off1, s2, q2, off2)
     n = len(off1) - 1
     filt = min_bp_quality > 0 or min_single_bp_quality > 0
     if filt and n and (np.any(np.diff(off1) == 0) or (paired and np.any(np.diff(off2) == 0))):
-        raise ValueError("prepare_packed: a record has no qualities")   # numpy: min() of an empty array
+        raise ValueError(f"{who}: a record has no qualities")   # numpy: min() of an empty array
     p, _alive = _params(prog, min_bp_quality, min_single_bp_quality, flash, with_quals)
     lib = _lib.load()
     if force_ops_output:
@@ -95,7 +106,7 @@ def prepare_packed(aligner: GpuAligner, s1: np.ndarray, q1: np.ndarray, off1: np
                          _lib.ptr(off2) if paired else None, n, ctypes.byref(res))
     if rc != 0:
         raise FrontError(lib.nwp_last_error().decode(errors="replace"), rc)
-    return _collect(aligner, lib, res, n, with_quals, with_packed)
+    return lib, res, n
 
 
 def _program(who: str, trim) -> TrimProgram:
@@ -131,6 +142,23 @@ def _params(prog: TrimProgram, min_bp_quality: int, min_single_bp_quality: int, 
     return p, alive
 
 
+def _stats(res, n: int) -> Dict[str, Union[int, float]]:
+    """The counters and kernel times of an nwp_result as PreparedBatch.stats names them."""
+    total, n_exc = int(res.total), int(res.n_exc)
+    c = [int(x) for x in res.counts]
+    t = [int(x) for x in res.trim]
+    stats: Dict[str, Union[int, float]] = {
+        "pairs": n, "filtered": c[FILTERED], "trimmed": c[TRIMMED], "not_combined": c[NOT_COMBINED],
+        "combined": c[COMBINED] + c[COMBINED_OUTIE], "innies": c[COMBINED], "outies": c[COMBINED_OUTIE],
+        # Trimmomatic's summary line, over the reads the filter kept
+        "trim_pairs": n - c[FILTERED], "both": t[0], "fwd_only": t[1], "rev_only": t[2], "dropped": t[3],
+        "bases": total, "exceptions": n_exc,
+    }
+    for k, name in enumerate(_lib.NWP_MS):
+        stats[name + "_ms"] = float(res.kernel_ms[k])
+    return stats
+
+
 def _collect(aligner: GpuAligner, lib, res, n: int, with_quals: bool, with_packed: bool) -> PreparedBatch:
     """The host's copies of a successful nwp_prepare / nwp_prepare_records; releases ``res``."""
     try:
@@ -153,17 +181,7 @@ def _collect(aligner: GpuAligner, lib, res, n: int, with_quals: bool, with_packe
             raise FrontError(lib.nwp_last_error().decode(errors="replace"), rc)
     finally:
         lib.nwp_release(ctypes.byref(res))
-    c = [int(x) for x in res.counts]
-    t = [int(x) for x in res.trim]
-    stats: Dict[str, Union[int, float]] = {
-        "pairs": n, "filtered": c[FILTERED], "trimmed": c[TRIMMED], "not_combined": c[NOT_COMBINED],
-        "combined": c[COMBINED] + c[COMBINED_OUTIE], "innies": c[COMBINED], "outies": c[COMBINED_OUTIE],
-        # Trimmomatic's summary line, over the reads the filter kept
-        "trim_pairs": n - c[FILTERED], "both": t[0], "fwd_only": t[1], "rev_only": t[2], "dropped": t[3],
-        "bases": total, "exceptions": n_exc,
-    }
-    for k, name in enumerate(_lib.NWP_MS):
-        stats[name + "_ms"] = float(res.kernel_ms[k])
+    stats = _stats(res, n)
     pb = PreparedBatch(status, src, buf, offsets, lens, quals,
                        PackedReads(packed, offsets, exc_pos, exc_byte, lens) if with_packed else None, stats)
     if m:
@@ -214,7 +232,16 @@ def prepare_fastq_device(aligner: GpuAligner, r1: str, r2: Optional[str] = None,
     and only R1's names come back.  A malformed record among the first ``min(n1, n2)`` (header,
     '+' line, line lengths, quality range) refuses the call with :class:`FrontError` (code -1),
     a sequence longer than 4096 bases anywhere in either file with code -3."""
-    prog = _program("prepare_fastq_device", trim)
+    return _fastq_device("prepare_fastq_device", lambda lib, res, n: _collect(aligner, lib, res, n, with_quals, with_packed),
+                         aligner, r1, r2, min_bp_quality, min_single_bp_quality, trim, flash, with_quals,
+                         force_ops_output)
+
+
+def _fastq_device(who: str, collect, aligner: GpuAligner, r1: str, r2: Optional[str], min_bp_quality: int,
+                  min_single_bp_quality: int, trim, flash, with_quals: bool, force_ops_output: bool):
+    """The files parsed on the GPU, nwp_prepare_records on the records, ``collect(lib, res, n)``
+    on the live result (a :class:`PreparedBatch` or a :class:`ResidentReads`), and the names."""
+    prog = _program(who, trim)
     lib = _lib.load()
     a = read_fastq_records(r1, aligner.device, strict=False, fetch=False)
     b = None
@@ -226,7 +253,7 @@ def prepare_fastq_device(aligner: GpuAligner, r1: str, r2: Optional[str] = None,
         if filt and n:   # as prepare_packed: the filter's mean of an empty read (a flagged record: refused below)
             for rec in (a, b):
                 if rec is not None and not 0 <= rec.info["first_bad"] < n and np.any(np.diff(rec.fetch_offsets()[:n + 1]) == 0):
-                    raise ValueError("prepare_fastq_device: a record has no qualities")
+                    raise ValueError(f"{who}: a record has no qualities")
         p, _alive = _params(prog, min_bp_quality, min_single_bp_quality, flash, with_quals)
         if force_ops_output:
             aligner.set_output("ops")
@@ -235,17 +262,125 @@ def prepare_fastq_device(aligner: GpuAligner, r1: str, r2: Optional[str] = None,
                                      ctypes.byref(res))
         if rc != 0:
             raise FrontError(lib.nwp_last_error().decode(errors="replace"), rc)
-        pb = _collect(aligner, lib, res, n, with_quals, with_packed)
+        pb = collect(lib, res, n)
         raw, name_off = a.fetch_names()
         raw, name_off = raw.tobytes(), name_off.tolist()
     finally:
         a.close()
         if b is not None:
             b.close()
-    names = []
+    names, heads = [], []
     for i in pb.src.tolist():
         h = raw[name_off[i]:name_off[i + 1]]
         if r2 is not None and h.endswith(b"/1"):
             h = h[:-2]
+        heads.append(h)
         names.append(fasta_name(b"@" + h))
+    if isinstance(pb, ResidentReads):
+        pb.headers = heads
     return pb, names
+
+
+class ResidentReads:
+    """The merged reads of one front-end call, still in HBM: a live ``nwp_result`` that another
+    stage reads where it lies (``demux.GpuDemultiplexer.assign_prepared``).  The host holds what
+    it needs to name and place the reads (``status``, ``src``, ``offsets``, ``lens``, ``stats``);
+    the text and the qualities are fetched only when asked for.  A context manager: ``close()``
+    releases the device arrays (``nwp_release``); the aligner keeps its batch."""
+
+    def __init__(self, aligner: GpuAligner, lib, res, n: int, with_quals: bool):
+        self._lib, self._res = lib, res
+        self.device = aligner.device
+        self.with_quals = bool(with_quals)
+        self.headers: Optional[List[bytes]] = None   # R1's header lines (FLASH's /1 cut), from prepare_fastq_resident
+        m = int(res.m)
+        try:
+            self.status = np.zeros(n, np.uint8)
+            self.offsets = np.zeros(m + 1, np.int64)
+            self.lens = np.zeros(m, np.uint16)
+            self.src = np.zeros(m, np.int64)
+            self._check(lib.nwp_fetch(ctypes.byref(res), _lib.ptr(self.status), _lib.ptr(self.offsets),
+                                      _lib.ptr(self.lens), _lib.ptr(self.src), None, None, None, None, None))
+        except Exception:
+            self.close()
+            raise
+        self.stats = _stats(res, n)
+        if m:
+            aligner.adopted(None, self.offsets)
+
+    def _check(self, rc: int) -> None:
+        if rc != 0:
+            raise FrontError(self._lib.nwp_last_error().decode(errors="replace"), rc)
+
+    def __len__(self) -> int:
+        return len(self.lens)
+
+    @property
+    def closed(self) -> bool:
+        return not self._res.handle
+
+    @property
+    def total(self) -> int:
+        return int(self.offsets[-1])
+
+    def result(self):
+        """The ``nwp_result`` (a :class:`crispresso_amd._lib.NwpResult`) for a C entry that takes it."""
+        return self._res
+
+    def _fetch(self, quals: bool) -> np.ndarray:
+        if self.closed:
+            raise FrontError("the reads were released", -1)
+        out = _lib.pinned_pool().array(self.total, np.uint8)
+        self._check(self._lib.nwp_fetch(ctypes.byref(self._res), None, None, None, None, None if quals else _lib.ptr(out),
+                                        _lib.ptr(out) if quals else None, None, None, None))
+        return out
+
+    def fetch_text(self) -> np.ndarray:
+        """The batch's text, dense (uint8, read j at ``offsets[j]:offsets[j + 1]``), copied to the host."""
+        return self._fetch(False)
+
+    def fetch_quals(self) -> np.ndarray:
+        """The batch's qualities, dense, ASCII (a call made with ``with_quals``)."""
+        if not self.with_quals:
+            raise FrontError("the call did not keep the qualities (with_quals)", -1)
+        return self._fetch(True)
+
+    def close(self) -> None:
+        if getattr(self, "_res", None) is not None and self._res.handle:
+            self._lib.nwp_release(ctypes.byref(self._res))
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # pragma: no cover
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def prepare_packed_resident(aligner: GpuAligner, s1: np.ndarray, q1: np.ndarray, off1: np.ndarray,
+                            s2: Optional[np.ndarray], q2: Optional[np.ndarray], off2: Optional[np.ndarray], *,
+                            min_bp_quality: int = 0, min_single_bp_quality: int = 0,
+                            trim: Union[None, str, List[str], TrimProgram] = None, flash: Optional[FlashOptions] = None,
+                            with_quals: bool = False, force_ops_output: bool = True) -> ResidentReads:
+    """:func:`prepare_packed` that leaves the merged reads in HBM: the same arguments (but
+    ``with_packed``), a :class:`ResidentReads` instead of the host's copies.  The aligner still
+    adopts the whole batch (for a pooled run any amplicon serves as its reference; the adoption is
+    a device-to-device copy that the first group's adoption overwrites)."""
+    lib, res, n = _call_packed("prepare_packed_resident", aligner, s1, q1, off1, s2, q2, off2, min_bp_quality,
+                               min_single_bp_quality, trim, flash, with_quals, force_ops_output)
+    return ResidentReads(aligner, lib, res, n, with_quals)
+
+
+def prepare_fastq_resident(aligner: GpuAligner, r1: str, r2: Optional[str] = None, *, min_bp_quality: int = 0,
+                           min_single_bp_quality: int = 0, trim: Union[None, str, List[str], TrimProgram] = None,
+                           flash: Optional[FlashOptions] = None, with_quals: bool = False,
+                           force_ops_output: bool = True) -> Tuple[ResidentReads, List[str]]:
+    """:func:`prepare_fastq_device` that leaves the merged reads in HBM: ``(ResidentReads, names)``."""
+    return _fastq_device("prepare_fastq_resident", lambda lib, res, n: ResidentReads(aligner, lib, res, n, with_quals),
+                         aligner, r1, r2, min_bp_quality, min_single_bp_quality, trim, flash, with_quals,
+                         force_ops_output)

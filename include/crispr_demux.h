@@ -89,6 +89,20 @@ int nwd_assign(nwd_ctx* c, const uint8_t* reads, const int64_t* offsets, int64_t
                int32_t both_strands, int32_t* which, uint8_t* strand, int32_t* votes, int32_t* rival,
                int64_t* counts, int64_t* n_assigned, int64_t* n_tie, int64_t* n_no_hit, float* kernel_ms);
 
+/* nwd_assign on the merged reads the front end left in HBM (a live nwp_result of nwp_prepare /
+ * nwp_prepare_records, include/crispr_front.h), with no upload: the dense text is copied device to
+ * device into the context's text buffer, behind the event recorded after the front end's packer,
+ * in nwd_assign's layout and nwd_assign's chunks (CRISPR_NWD_CHUNK applies), and assigned by the
+ * same kernel.  A read whose tally overflowed is copied down alone and decided by the host path.
+ * Read r is the result's read r (its offsets are nwp_fetch's); n is its m.  Outputs as nwd_assign.
+ * Afterwards nwd_gather, nwd_pack and nwd_adopt_group behave exactly as after nwd_assign of the
+ * same text, and the result may be released at once.  A null or released result, or one on
+ * another device, is NW_E_INVALID; a call before nwd_set_amplicons NW_E_STATE; m == 0 returns
+ * zeros without touching the GPU.  Synchronous. */
+int nwd_assign_prepared(nwd_ctx* c, const struct nwp_result* res, int32_t min_hits, int32_t both_strands,
+                        int32_t* which, uint8_t* strand, int32_t* votes, int32_t* rival, int64_t* counts,
+                        int64_t* n_assigned, int64_t* n_tie, int64_t* n_no_hit, float* kernel_ms);
+
 /* The assigned reads of the last nwd_assign, grouped: group_offsets int64 [n_refs + 1] (group g
  * is the gathered reads group_offsets[g] .. group_offsets[g + 1]), order int64 [n_assigned] the
  * input index of each gathered read, text_offsets int64 [n_assigned + 1] into text [text_cap],
