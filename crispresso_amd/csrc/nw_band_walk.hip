@@ -378,23 +378,35 @@ __device__ void walk_lanes(const KernelArgs& a, long long klo, long long khi, un
                 const long long off = h ? (long long)(((unsigned long long)(unsigned)ho.w << 32) | (unsigned)ho.z)
                                         : (long long)(((unsigned long long)(unsigned)ho.y << 32) | (unsigned)ho.x);
                 // mismatches of amplicon bytes [ia, ia + n) against read bytes [jb, jb + n) (plain: A C G T,
-                // case folded), dword compares
-                auto count_mis = [&](int ia, int jb, int n) -> int {
+                // case folded), dword compares, NW_MIS_UNROLL dwords' loads together.  The count stops once
+                // 9 sc5 c is past `slack`: the caller asks only whether it stays within it, an unrelated
+                // diagonal is past it within its first dwords, and every further batch is a dependent global
+                // round trip (to the end of a 250-base diagonal: 8 of them, for each diagonal in turn)
+                auto count_mis = [&](int ia, int jb, int n, int slack) -> int {
                     int c = 0;
                     const unsigned char* rp = a.reads + off + jb;
                     const int ra = (int)((uintptr_t)rp & 3), aa = ia & 3;
                     const unsigned* rw = (const unsigned*)(rp - ra);
                     const unsigned* aw = (const unsigned*)(amp_lds + (ia - aa));
+                    const int nwd = (n + 3) >> 2;   // the last dword index read (the same with and without the stop)
                     unsigned rlo = rw[0], alo = aw[0];
-#pragma unroll NW_MIS_UNROLL
-                    for (int t = 0; t < n; t += 4) {
-                        const unsigned rhi = rw[(t >> 2) + 1], ahi = aw[(t >> 2) + 1];
-                        unsigned x = (__builtin_amdgcn_alignbyte(rhi, rlo, ra) ^ __builtin_amdgcn_alignbyte(ahi, alo, aa)) &
-                                     0xdfdfdfdfu;
-                        if (n - t < 4) x &= 0xffffffffu >> (8 * (4 - (n - t)));
-                        c += 4 - __builtin_popcount(zero_bytes(x));
-                        rlo = rhi;
-                        alo = ahi;
+                    for (int w0 = 0; w0 < nwd && 9 * sc5 * c <= slack; w0 += NW_MIS_UNROLL) {
+                        unsigned rr[NW_MIS_UNROLL], av[NW_MIS_UNROLL];
+#pragma unroll
+                        for (int u = 0; u < NW_MIS_UNROLL; ++u) {
+                            rr[u] = rw[min(w0 + u + 1, nwd)];
+                            av[u] = aw[min(w0 + u + 1, nwd)];
+                        }
+#pragma unroll
+                        for (int u = 0; u < NW_MIS_UNROLL; ++u) {
+                            const int left = n - 4 * (w0 + u);   // bytes of this dword inside the diagonal
+                            unsigned x = (__builtin_amdgcn_alignbyte(rr[u], rlo, ra) ^ __builtin_amdgcn_alignbyte(av[u], alo, aa)) &
+                                         0xdfdfdfdfu;
+                            x &= left >= 4 ? 0xffffffffu : (left <= 0 ? 0u : 0xffffffffu >> (8 * (4 - left)));
+                            c += 4 - __builtin_popcount(zero_bytes(x));
+                            rlo = rr[u];
+                            alo = av[u];
+                        }
                     }
                     return c;
                 };
@@ -413,7 +425,8 @@ __device__ void walk_lanes(const KernelArgs& a, long long klo, long long khi, un
                                 const int P = diag_pairs(La, Lb, d);
                                 if (P <= 0 || m * P < score) break;
                                 const int i0 = d >= 0 ? 0 : -d, j0 = d >= 0 ? d : 0;
-                                if (m * P - 9 * sc5 * count_mis(i0, j0, P) >= score) {
+                                // m P - 9 sc5 mis_d >= score: the diagonal reaches the score
+                                if (9 * sc5 * count_mis(i0, j0, P, m * P - score) <= m * P - score) {
                                     cert = false;
                                     break;
                                 }
