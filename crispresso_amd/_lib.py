@@ -90,10 +90,11 @@ NWS_SLOT_NAMES = ("n", "n_total", "n_unmodified", "n_modified", "n_repaired", "n
 REGION_EXPORTS = (
     "nwr_read_bam", "nwr_bam_free", "nwr_bam_count", "nwr_bam_data", "nwr_bam_offsets", "nwr_bam_n_ref",
     "nwr_bam_ref_names", "nwr_bam_ref_lens", "nwr_bam_text", "nwr_create", "nwr_destroy", "nwr_last_error",
-    "nwr_extract", "nwr_fetch", "nwr_release", "nwr_discover", "nwr_fetch_regions",
+    "nwr_extract", "nwr_fetch", "nwr_release", "nwr_discover", "nwr_fetch_regions", "nwr_packed_info",
+    "nwr_fetch_packed", "nwr_adopt_region",
 )
 NWR_MAX_REGIONS = 1 << 20
-NWR_BY_REFERENCE, NWR_EQX_AS_MATCH = 1, 2
+NWR_BY_REFERENCE, NWR_EQX_AS_MATCH, NWR_PACKED = 1, 2, 4
 
 # Every symbol include/crispr_flash.h declares.
 FLASH_EXPORTS = ("nwf_merge_batch", "nwf_last_error")
@@ -378,6 +379,9 @@ def load() -> ctypes.CDLL:
         "nwr_release": (None, [POINTER(NwrResult)]),
         "nwr_discover": (c_int, [ctx_p, c_void_p, c_int32, c_int64, POINTER(NwrResult)]),
         "nwr_fetch_regions": (c_int, [POINTER(NwrResult), c_void_p, c_void_p, c_void_p]),
+        "nwr_packed_info": (c_int, [POINTER(NwrResult), c_void_p, c_void_p, POINTER(c_int64), POINTER(c_float)]),
+        "nwr_fetch_packed": (c_int, [POINTER(NwrResult), c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64)]),
+        "nwr_adopt_region": (c_int, [POINTER(NwrResult), ctx_p, c_int64]),
         "nw_synth_offsets": (c_int64, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,
                                         c_int32]),
         "nw_synth_reads": (c_int, [c_char_p, c_int32, c_int64, c_int64, ctypes.c_uint64, c_void_p, c_void_p,

@@ -39,6 +39,31 @@
 //            the hit (region, record) lands at its scanned index.  order and emit follow as above.
 // Which slot a key got depends on arrival order; the slot never leaves this file: the host orders
 // by key, and the hit list is in record order.
+//
+// NWR_PACKED leaves the reads in HBM as the aligner's 2-bit batch (pack_result).  Emit is not run:
+// no ASCII base and no quality is made.  The stream is region-major across the chunks, and only
+// one chunk's records are on the device at a time, so a region's run from chunk c and its run
+// from chunk c + 1 can meet inside a dword, and a chunk's runs are scattered over the stream.
+// The shape chosen: all chunks' hit lists are collected and merged on the host first (16 bytes a
+// hit, as before), which fixes every hit's final position; then one sweep per chunk (the chunk is
+// still resident in a one-chunk call, else uploaded again) over the dwords that hold a base of it:
+//   words   a thread per dword of a segment (a maximal run of final hits from this chunk): its
+//           segment by binary search of the segments' thread bases, its hit by a bounded binary
+//           search of the final offsets.  16 bases in one hit are 8 or 9 consecutive record bytes
+//           by the parity of st + k: aligned dword loads (grp::load_dword), the halves of every
+//           byte swapped at once, a shift by one code when odd.  Codes 1 2 8 4 are 0 1 2 3.  A
+//           dword that the segment fills is stored once, whole; a dword that segments share is
+//           OR-ed into the stream, which is zeroed once per call.  Exceptions set their bit in a
+//           mask of one bit a base (OR, zeroed once) and are counted into sums[block].
+//   scan    one block: the exclusive scan of the block sums; the chunk's count goes to the host.
+//   exc     the second walk: (position, letter) into the chunk's own list at the scanned index.
+// When the mask is whole: rank sums (the mask's bits per 256 words), scan, place (every listed
+// exception to the slot that is the number of mask bits before its position: ascending positions
+// whatever chunk a base came from), bounds (the same rank of every region's first position).
+// Why this is deterministic: a final position belongs to one hit of one chunk, so every bit of
+// the stream and of the mask is written by one thread, and integer OR into zeroed words does not
+// depend on order; the places come from the finished mask alone; the chunk lists' indices come
+// from scans.  No float, no arrival order.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -46,6 +71,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <numeric>
 #include <string>
 #include <vector>
@@ -53,8 +79,10 @@
 #include "../../include/crispr_nw.h"
 #include "../../include/crispr_regions.h"
 #include "group_device.h"
+#include "front_device.h"
 #include "host_dev.h"
 #include "nw_bam.h"
+#include "nw_device.h"
 
 namespace nwr {
 
@@ -487,6 +515,232 @@ __global__ __launch_bounds__(256) void nwr_emit_kernel(const uint8_t* data, cons
     quals[t] = qw;
 }
 
+// ---- NWR_PACKED: the hits as the aligner's 2-bit batch ----------------------------------------
+
+constexpr int kPackBlk = 256;
+constexpr int kRankBlk = 256;                  // mask words (32 positions each) per rank sum
+
+// A run of consecutive final hits whose records lie in one chunk: final positions [p_lo, p_hi),
+// p_lo < p_hi; its dwords are the threads [t0, t0 + (p_hi + 15) / 16 - p_lo / 16) of the sweep.
+struct Seg {
+    int64_t h_lo, h_hi, t0;
+    uint32_t p_lo, p_hi;
+};
+
+struct PackArgs {
+    const uint8_t* data;       // the chunk's records
+    const EmitHit* eh;         // [n_hits] of the whole call, final order; seq within the hit's own chunk
+    const uint32_t* ooff;      // [n_hits + 1] final positions
+    const Seg* seg;            // the chunk's segments, ascending
+    int32_t nseg;
+    int64_t nthreads;          // the segments' dwords
+    uint32_t* words;           // the call's stream, zeroed once
+    uint32_t* mask;            // bit p % 32 of word p / 32: position p is an exception; zeroed once
+    uint32_t* sums;            // [blocks] the sweep's exceptions per block, then their exclusive prefix
+    int64_t blocks;
+    int64_t* exc_pos;          // the chunk's own list, in sweep order
+    uint8_t* exc_byte;
+    int64_t n_exc;
+};
+
+// The BAM codes of final positions 16 w + k, k in [k0, k1), code k in bits 4 k of nib.
+struct Piece {
+    uint64_t nib;
+    int64_t w;
+    int k0, k1;
+};
+
+__device__ __forceinline__ Piece piece_at(const PackArgs& a, int64_t t) {
+    int lo = 0, hi = a.nseg;                               // the last segment with t0 <= t
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (a.seg[mid].t0 <= t) lo = mid; else hi = mid;
+    }
+    const Seg s = a.seg[lo];
+    Piece pc;
+    pc.w = (int64_t)(s.p_lo >> 4) + (t - s.t0);
+    const int64_t p0 = 16 * pc.w;
+    const int64_t b0 = p0 > (int64_t)s.p_lo ? p0 : (int64_t)s.p_lo;
+    const int64_t b1 = p0 + 16 < (int64_t)s.p_hi ? p0 + 16 : (int64_t)s.p_hi;      // b0 < b1: the dword holds a base of s
+    pc.k0 = (int)(b0 - p0);
+    pc.k1 = (int)(b1 - p0);
+    pc.nib = 0;
+    int64_t hl = s.h_lo, hh = s.h_hi;                      // the last hit of the segment with ooff <= b0
+    while (hh - hl > 1) {                                  // (at most 31 steps: a chunk has under 2^31 hits)
+        const int64_t mid = (hl + hh) >> 1;
+        if ((int64_t)a.ooff[mid] <= b0) hl = mid; else hh = mid;
+    }
+    int64_t h = hl;
+    EmitHit e = a.eh[h];
+    int64_t h0 = a.ooff[h], h1 = a.ooff[h + 1];
+    if (b1 - b0 == 16 && b1 <= h1) {                       // all 16 in this hit: 8 bytes, 9 when q is odd
+        const int64_t q = (int64_t)e.st + (b0 - h0);
+        const uint8_t* p = a.data + e.seq + (q >> 1);
+        const int64_t L = 8 + (q & 1);
+        uint64_t v = (uint64_t)grp::load_dword(p, 0, L) | ((uint64_t)grp::load_dword(p, 1, L) << 32);
+        v = ((v & 0x0F0F0F0F0F0F0F0Full) << 4) | ((v >> 4) & 0x0F0F0F0F0F0F0F0Full);      // the first base of a byte is its high half
+        if (q & 1) v = (v >> 4) | ((uint64_t)(grp::load_dword(p, 2, L) >> 4) << 60);
+        pc.nib = v;
+        return pc;
+    }
+    for (int64_t b = b0; b < b1; ++b) {                    // the end of one hit and the start of the next
+        if (b >= h1) {
+            do {
+                ++h;
+                h1 = a.ooff[h + 1];
+            } while (b >= h1);                             // (b < p_hi = ooff[h_hi]: ends inside the segment)
+            h0 = a.ooff[h];
+            e = a.eh[h];
+        }
+        const int64_t q = (int64_t)e.st + (b - h0);
+        const uint32_t two = a.data[e.seq + (q >> 1)];
+        pc.nib |= (uint64_t)((q & 1) ? (two & 15u) : (two >> 4)) << (4 * (b - p0));
+    }
+    return pc;
+}
+
+// Codes 1, 2, 8, 4 (A, C, T, G) are bases 0, 1, 2, 3; every other code is an exception.
+constexpr uint32_t kBaseOf = (1u << 4) | (2u << 16) | (3u << 8), kIsBase = 0x116u;
+
+// One thread per dword of the chunk's segments.  A dword that one segment fills is stored once;
+// a dword that segments share (of this chunk or of others) is OR-ed into the zeroed stream.
+__global__ __launch_bounds__(kPackBlk) void nwr_pack_words_kernel(const PackArgs a) {
+    __shared__ uint32_t part[kPackBlk / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t t = (int64_t)blockIdx.x * kPackBlk + threadIdx.x;
+    uint32_t ne = 0;
+    if (t < a.nthreads) {
+        const Piece pc = piece_at(a, t);
+        uint32_t out = 0, em = 0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const uint32_t n = (uint32_t)(pc.nib >> (4 * k)) & 15u;
+            if (k >= pc.k0 && k < pc.k1) {
+                if ((kIsBase >> n) & 1u) out |= ((kBaseOf >> (2 * n)) & 3u) << (2 * k);
+                else em |= 1u << k;
+            }
+        }
+        if (pc.k1 - pc.k0 == 16) a.words[pc.w] = out;
+        else if (out) atomicOr(&a.words[pc.w], out);       // (an OR: no order shows)
+        if (em) atomicOr(&a.mask[pc.w >> 1], em << (16 * (int)(pc.w & 1)));
+        ne = (uint32_t)__popc(em);
+    }
+    for (int s = 32; s > 0; s >>= 1) ne += __shfl_xor(ne, s);
+    if (lane == 0) part[wave] = ne;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int v = 0; v < kPackBlk / 64; ++v) s += part[v];
+        a.sums[blockIdx.x] = s;
+    }
+}
+
+// One block: sums[b] becomes the exclusive prefix over the blocks before b; *total the sum.
+__global__ __launch_bounds__(kScanBlk) void nwr_pack_scan_kernel(uint32_t* sums, int64_t blocks, int64_t* total) {
+    __shared__ uint32_t sh[2][kScanBlk];
+    const int t = threadIdx.x;
+    const int64_t per = (blocks + kScanBlk - 1) / kScanBlk;
+    const int64_t lo = std::min<int64_t>(blocks, t * per), hi = std::min<int64_t>(blocks, lo + per);
+    uint32_t mine = 0;
+    for (int64_t b = lo; b < hi; ++b) mine += sums[b];
+    int cur = 0;
+    sh[0][t] = mine;
+    __syncthreads();
+    for (int d = 1; d < kScanBlk; d <<= 1) {
+        sh[cur ^ 1][t] = sh[cur][t] + (t >= d ? sh[cur][t - d] : 0u);
+        cur ^= 1;
+        __syncthreads();
+    }
+    uint32_t run = sh[cur][t] - mine;
+    if (t == kScanBlk - 1) *total = (int64_t)sh[cur][t];
+    for (int64_t b = lo; b < hi; ++b) {
+        const uint32_t v = sums[b];
+        sums[b] = run;
+        run += v;
+    }
+}
+
+// The second walk: the chunk's exceptions (position, letter) at the block's base + the
+// exceptions of the block's threads before this one.
+__global__ __launch_bounds__(kPackBlk) void nwr_pack_exc_kernel(const PackArgs a) {
+    __shared__ uint32_t part[kPackBlk / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int64_t t = (int64_t)blockIdx.x * kPackBlk + threadIdx.x;
+    Piece pc{0, 0, 0, 0};
+    uint32_t em = 0;
+    if (t < a.nthreads) {
+        pc = piece_at(a, t);
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (k >= pc.k0 && k < pc.k1 && !((kIsBase >> ((uint32_t)(pc.nib >> (4 * k)) & 15u)) & 1u)) em |= 1u << k;
+    }
+    const uint32_t ne = (uint32_t)__popc(em);
+    uint32_t x = ne;
+    for (int s = 1; s < 64; s <<= 1) {
+        const uint32_t y = __shfl_up(x, s);
+        if (lane >= s) x += y;
+    }
+    if (lane == 63) part[wave] = x;
+    __syncthreads();
+    int64_t slot = (int64_t)a.sums[blockIdx.x] + (x - ne);
+    for (int v = 0; v < wave; ++v) slot += part[v];
+    for (; em; em &= em - 1) {
+        const int k = __ffs((int)em) - 1;
+        const uint32_t code = (uint32_t)(pc.nib >> (4 * k)) & 15u;
+        if (slot < a.n_exc) {                              // (always: the words kernel's sum)
+            a.exc_pos[slot] = 16 * pc.w + k;
+            a.exc_byte[slot] = (uint8_t)(((code & 8u) ? kNibHi : kNibLo) >> (8 * (code & 7u)));
+        }
+        ++slot;
+    }
+}
+
+// The exceptions of every kRankBlk mask words, for the scan.
+__global__ __launch_bounds__(kRankBlk) void nwr_rank_sums_kernel(const uint32_t* mask, uint32_t* rsums) {
+    __shared__ uint32_t part[kRankBlk / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t v = (uint32_t)__popc(mask[(int64_t)blockIdx.x * kRankBlk + threadIdx.x]);      // (the mask is padded to whole blocks)
+    for (int s = 32; s > 0; s >>= 1) v += __shfl_xor(v, s);
+    if (lane == 0) part[wave] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t s = 0;
+        for (int w = 0; w < kRankBlk / 64; ++w) s += part[w];
+        rsums[blockIdx.x] = s;
+    }
+}
+
+// The exceptions before position p < 32 * (mask words): the place of p's own in the final list.
+__device__ inline int64_t rank_of(const uint32_t* mask, const uint32_t* rsums, int64_t p) {
+    const int64_t word = p >> 5, first = word & ~(int64_t)(kRankBlk - 1);
+    int64_t r = rsums[word / kRankBlk];
+    for (int64_t i = first; i < word; ++i) r += __popc(mask[i]);      // (under kRankBlk steps)
+    return r + __popc(mask[word] & ((1u << (p & 31)) - 1u));
+}
+
+// A chunk's list to its places in the call's: ascending positions whatever chunk a base came from.
+__global__ __launch_bounds__(256) void nwr_exc_place_kernel(const int64_t* lpos, const uint8_t* lbyte, int64_t n,
+                                                            const uint32_t* mask, const uint32_t* rsums, int64_t n_exc,
+                                                            int64_t* exc_pos, uint8_t* exc_byte) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t p = lpos[i], slot = rank_of(mask, rsums, p);
+    if (slot < n_exc) {                                    // (always: the mask holds n_exc bits)
+        exc_pos[slot] = p;
+        exc_byte[slot] = lbyte[i];
+    }
+}
+
+// gexc[g] = the exceptions before region g's first position rpos[g], g in [0, n_regions].
+__global__ __launch_bounds__(256) void nwr_exc_bounds_kernel(const int64_t* rpos, int64_t n, int64_t total,
+                                                             const uint32_t* mask, const uint32_t* rsums, int64_t n_exc,
+                                                             int64_t* gexc) {
+    const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (g >= n) return;
+    const int64_t p = rpos[g];
+    gexc[g] = p >= total ? n_exc : rank_of(mask, rsums, p);
+}
+
 // The hits of one chunk (or of the whole call) in region-major order.
 struct Hits {
     std::vector<int32_t> reg, st, en;
@@ -502,6 +756,23 @@ struct Result {
     std::vector<nwr_region> regions;
     std::vector<int64_t> n_records;
     int64_t stats[4] = {0, 0, 0, 0};
+    // NWR_PACKED: the batch in HBM, the result's own (it outlives the context that made it)
+    bool packed = false;
+    int device = 0;
+    int64_t n_exc = 0;
+    float pack_ms = 0.0f;
+    std::vector<uint16_t> lens16;
+    std::vector<int64_t> gexc;      // [n_regions + 1]
+    hd::DevBuf<uint32_t> d_words;
+    hd::DevBuf<uint16_t> d_lens16;
+    hd::DevBuf<int64_t> d_exc_pos, d_gbase;
+    hd::DevBuf<uint8_t> d_exc_byte;
+    hipEvent_t ready = nullptr;     // recorded behind the packer
+    ~Result() {
+        if (!packed) return;
+        (void)hipSetDevice(device);
+        if (ready) (void)hipEventDestroy(ready);
+    }
 };
 
 }  // namespace nwr
@@ -521,6 +792,10 @@ struct nwr_ctx : hd::DevContext {
     hd::DevBuf<uint32_t> d_tcount, d_slot, d_lslot;
     hd::DevBuf<int32_t> d_map, d_lreg;
     hd::DevBuf<nwr::Listed> d_list;
+    // NWR_PACKED: what the packer needs beside the result's own buffers
+    hd::DevBuf<nwr::Seg> d_seg;
+    hd::DevBuf<uint32_t> d_mask, d_psums, d_rsums;
+    hd::DevBuf<int64_t> d_ptotal, d_rpos, d_gexc;
 };
 
 namespace {
@@ -620,7 +895,8 @@ int emit_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, int32_t f
                     (long long)nh, (long long)r0, (long long)r1);
     if (nh == 0) return NW_OK;      // (a chunk of off-target records alone is not uploaded again)
     std::vector<int64_t> off;
-    const int rc = upload_chunk(c, bam, r0, r1, false, &off, resident ? nullptr : upload_ms);
+    // (a packed call's write kernel reads no record byte: the packer uploads the chunk when its turn comes)
+    const int rc = upload_chunk(c, bam, r0, r1, false, &off, resident || (flags & NWR_PACKED) ? nullptr : upload_ms);
     if (rc != NW_OK) return rc;
     a.data = c->d_data.p;
     static const std::vector<int32_t> no_perm;
@@ -734,7 +1010,7 @@ int finish_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, const s
     if (total >= ((int64_t)1 << 32))
         return fail(c, NW_E_UNSUPPORTED, "%lld output bytes in the chunk of records %lld to %lld: under 2^32 (use a smaller CRISPR_NWR_CHUNK)",
                     (long long)total, (long long)r0, (long long)r1);
-    if (total == 0) return NW_OK;
+    if (total == 0 || (a.flags & NWR_PACKED)) return NW_OK;      // (packed: the bases are read by pack_result)
     std::vector<uint32_t> ooff((size_t)nh + 1);
     for (int64_t k = 0; k <= nh; ++k) ooff[(size_t)k] = (uint32_t)out->toff[(size_t)k];
     const int64_t words = (total + 3) / 4;
@@ -762,7 +1038,7 @@ int finish_chunk(nwr_ctx* c, const nwr_bam* bam, int64_t r0, int64_t r1, const s
 }
 
 // The chunks' hits (each region-major) as one region-major list, the chunks in order in a region.
-void merge_chunks(std::vector<nwr::Hits>& chunks, int64_t n_regions, nwr::Result* res) {
+void merge_chunks(std::vector<nwr::Hits>& chunks, int64_t n_regions, nwr::Result* res, bool packed) {
     std::vector<int64_t>& ro = res->region_off;
     ro.assign((size_t)n_regions + 1, 0);
     for (const nwr::Hits& h : chunks)
@@ -784,6 +1060,7 @@ void merge_chunks(std::vector<nwr::Hits>& chunks, int64_t n_regions, nwr::Result
     for (int pass = 0; pass < 2; ++pass) {
         if (pass == 1) {
             for (size_t k = 0; k < nh; ++k) o.toff[k + 1] += o.toff[k];
+            if (packed) break;      // (no chunk holds text)
             o.text.resize((size_t)o.toff[nh]);
             o.quals.resize((size_t)o.toff[nh]);
             std::copy(ro.begin(), ro.end() - 1, cur.begin());
@@ -813,6 +1090,190 @@ void merge_chunks(std::vector<nwr::Hits>& chunks, int64_t n_regions, nwr::Result
     }
 }
 
+// NWR_PACKED, after merge_chunks: the merged hits of R as the aligner's batch in R's own buffers.
+// ranges are the call's chunks; a one-chunk call still has its records in d_data.
+int pack_result(nwr_ctx* c, const nwr_bam* bam, const std::vector<std::pair<int64_t, int64_t>>& ranges, nwr::Result* R,
+                float* upload_ms) {
+    hipStream_t st = c->stream;
+    const nwr::Hits& h = R->h;
+    const int64_t nh = (int64_t)h.reg.size(), total = h.toff.back(), n_regions = (int64_t)R->region_off.size() - 1;
+    R->packed = true;
+    R->device = c->device;
+    R->gexc.assign((size_t)n_regions + 1, 0);
+    R->lens16.resize((size_t)nh);
+    for (int64_t k = 0; k < nh; ++k) {
+        const int64_t len = h.toff[(size_t)k + 1] - h.toff[(size_t)k];
+        if (len > 65535)
+            return fail(c, NW_E_UNSUPPORTED, "record %lld gives a read of %lld bases: a packed read holds at most 65535",
+                        (long long)h.src[(size_t)k], (long long)len);
+        R->lens16[(size_t)k] = (uint16_t)len;
+    }
+    if ((uint64_t)total >= (1ull << 32))
+        return fail(c, NW_E_UNSUPPORTED, "%lld bases in the call: 2^32 or more in one packed call are not supported",
+                    (long long)total);
+    if (nh == 0) return NW_OK;
+    HIP_TRY(c, hipEventCreate(&R->ready));
+    const int64_t nwords = (total + 15) / 16;
+    const int64_t mblocks = ((total + 31) / 32 + nwr::kRankBlk - 1) / nwr::kRankBlk + 1, mwords = mblocks * nwr::kRankBlk;
+    HIP_TRY(c, R->d_words.reserve((size_t)nwords + 16));      // (the adoption's copies stay inside)
+    HIP_TRY(c, R->d_lens16.reserve((size_t)nh));
+    HIP_TRY(c, hipMemsetAsync(R->d_words.p, 0, sizeof(uint32_t) * (size_t)(nwords + 16), st));
+    HIP_TRY(c, hipMemcpyAsync(R->d_lens16.p, R->lens16.data(), sizeof(uint16_t) * (size_t)nh, hipMemcpyHostToDevice, st));
+    if (total == 0) {
+        HIP_TRY(c, hipEventRecord(R->ready, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+        return NW_OK;
+    }
+
+    // every final hit: where its bases start within its own chunk's records, and its chunk
+    std::vector<nwr::EmitHit> eh((size_t)nh);
+    std::vector<uint32_t> ooff((size_t)nh + 1);
+    std::vector<std::vector<nwr::Seg>> segs(ranges.size());
+    std::vector<int64_t> starts(ranges.size());
+    for (size_t x = 0; x < ranges.size(); ++x) starts[x] = ranges[x].first;
+    int64_t run_lo = 0;
+    size_t run_chunk_ix = 0;
+    auto close_run = [&](int64_t k) {      // final hits [run_lo, k) lie in chunk run_chunk_ix
+        if (k > run_lo && h.toff[(size_t)k] > h.toff[(size_t)run_lo])
+            segs[run_chunk_ix].push_back(nwr::Seg{run_lo, k, 0, (uint32_t)h.toff[(size_t)run_lo], (uint32_t)h.toff[(size_t)k]});
+    };
+    for (int64_t k = 0; k < nh; ++k) {
+        const int64_t rec = h.src[(size_t)k];
+        const size_t x = (size_t)(std::upper_bound(starts.begin(), starts.end(), rec) - starts.begin()) - 1;
+        if (k == 0) run_chunk_ix = x;
+        if (x != run_chunk_ix) {
+            close_run(k);
+            run_lo = k;
+            run_chunk_ix = x;
+        }
+        const uint8_t* r = bam->data.data() + bam->off[(size_t)rec];
+        const int64_t l_seq = (int32_t)h32(r + nw_bam::kLSeq);
+        eh[(size_t)k].seq = bam->off[(size_t)rec] - bam->off[(size_t)ranges[x].first] + nw_bam::kName + r[nw_bam::kLReadName] +
+                            4 * (int64_t)h16(r + nw_bam::kNCigar);
+        eh[(size_t)k].l_seq = (int32_t)l_seq;
+        eh[(size_t)k].st = (int32_t)std::min<int64_t>(h.st[(size_t)k], l_seq);
+        ooff[(size_t)k] = (uint32_t)h.toff[(size_t)k];
+    }
+    close_run(nh);
+    ooff[(size_t)nh] = (uint32_t)total;
+
+    HIP_TRY(c, c->d_eh.reserve((size_t)nh));
+    HIP_TRY(c, c->d_ooff.reserve((size_t)nh + 1));
+    HIP_TRY(c, c->d_mask.reserve((size_t)mwords));
+    HIP_TRY(c, c->d_rsums.reserve((size_t)mblocks));
+    HIP_TRY(c, c->d_ptotal.reserve(1));
+    HIP_TRY(c, hipMemcpyAsync(c->d_eh.p, eh.data(), sizeof(nwr::EmitHit) * (size_t)nh, hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemcpyAsync(c->d_ooff.p, ooff.data(), sizeof(uint32_t) * (size_t)(nh + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(c, hipMemsetAsync(c->d_mask.p, 0, sizeof(uint32_t) * (size_t)mwords, st));
+
+    // a sweep per chunk; its exceptions wait in a list of their own for the mask to be whole
+    struct Local {
+        hd::DevBuf<int64_t> pos;
+        hd::DevBuf<uint8_t> byte;
+        int64_t n = 0;
+    };
+    std::vector<std::unique_ptr<Local>> locals;
+    float ms = 0.0f;
+    int64_t sum_exc = 0;
+    for (size_t x = 0; x < ranges.size(); ++x) {
+        std::vector<nwr::Seg>& sg = segs[x];
+        if (sg.empty()) continue;
+        int64_t nt = 0;
+        for (nwr::Seg& s : sg) {
+            s.t0 = nt;
+            nt += (int64_t)(((uint64_t)s.p_hi + 15) / 16) - (int64_t)(s.p_lo / 16);
+        }
+        if (ranges.size() > 1) {
+            std::vector<int64_t> off;
+            const int rc = upload_chunk(c, bam, ranges[x].first, ranges[x].second, false, &off, upload_ms);
+            if (rc != NW_OK) return rc;
+        }
+        nwr::PackArgs a{};
+        a.data = c->d_data.p;
+        a.eh = c->d_eh.p;
+        a.ooff = c->d_ooff.p;
+        a.nseg = (int32_t)sg.size();
+        a.nthreads = nt;
+        a.words = R->d_words.p;
+        a.mask = c->d_mask.p;
+        a.blocks = (nt + nwr::kPackBlk - 1) / nwr::kPackBlk;
+        HIP_TRY(c, c->d_seg.reserve(sg.size()));
+        HIP_TRY(c, c->d_psums.reserve((size_t)a.blocks));
+        HIP_TRY(c, hipMemcpyAsync(c->d_seg.p, sg.data(), sizeof(nwr::Seg) * sg.size(), hipMemcpyHostToDevice, st));
+        a.seg = c->d_seg.p;
+        a.sums = c->d_psums.p;
+        HIP_TRY(c, hipEventRecord(c->ev[0], st));
+        hipLaunchKernelGGL(nwr::nwr_pack_words_kernel, dim3((unsigned)a.blocks), dim3(nwr::kPackBlk), 0, st, a);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(nwr::nwr_pack_scan_kernel, dim3(1), dim3(nwr::kScanBlk), 0, st, a.sums, a.blocks, c->d_ptotal.p);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->ev[1], st));
+        int64_t ne = 0;
+        HIP_TRY(c, hipMemcpyAsync(&ne, c->d_ptotal.p, sizeof ne, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipStreamSynchronize(st));      // (the segments above are read by the copy)
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        R->pack_ms += ms;
+        if (ne < 0 || ne > total - sum_exc) return fail(c, NW_E_STATE, "inconsistent exception count");
+        if (ne == 0) continue;
+        sum_exc += ne;
+        locals.emplace_back(new Local());
+        Local& l = *locals.back();
+        l.n = ne;
+        HIP_TRY(c, l.pos.reserve((size_t)ne));
+        HIP_TRY(c, l.byte.reserve((size_t)ne));
+        a.n_exc = ne;
+        a.exc_pos = l.pos.p;
+        a.exc_byte = l.byte.p;
+        HIP_TRY(c, hipEventRecord(c->ev[0], st));
+        hipLaunchKernelGGL(nwr::nwr_pack_exc_kernel, dim3((unsigned)a.blocks), dim3(nwr::kPackBlk), 0, st, a);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->ev[1], st));
+        HIP_TRY(c, hipStreamSynchronize(st));      // (the next chunk overwrites d_data)
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        R->pack_ms += ms;
+    }
+    if (sum_exc > 0) {
+        // the mask is whole: every exception's place in the call's list, and the regions' bounds
+        std::vector<int64_t> rpos((size_t)n_regions + 1);
+        for (int64_t g = 0; g <= n_regions; ++g) rpos[(size_t)g] = h.toff[(size_t)R->region_off[(size_t)g]];
+        HIP_TRY(c, R->d_exc_pos.reserve((size_t)sum_exc));
+        HIP_TRY(c, R->d_exc_byte.reserve((size_t)sum_exc));
+        HIP_TRY(c, c->d_rpos.reserve((size_t)n_regions + 1));
+        HIP_TRY(c, c->d_gexc.reserve((size_t)n_regions + 1));
+        HIP_TRY(c, hipMemcpyAsync(c->d_rpos.p, rpos.data(), sizeof(int64_t) * (size_t)(n_regions + 1), hipMemcpyHostToDevice, st));
+        HIP_TRY(c, hipEventRecord(c->ev[0], st));
+        hipLaunchKernelGGL(nwr::nwr_rank_sums_kernel, dim3((unsigned)mblocks), dim3(nwr::kRankBlk), 0, st,
+                           (const uint32_t*)c->d_mask.p, c->d_rsums.p);
+        HIP_TRY(c, hipGetLastError());
+        hipLaunchKernelGGL(nwr::nwr_pack_scan_kernel, dim3(1), dim3(nwr::kScanBlk), 0, st, c->d_rsums.p, mblocks, c->d_ptotal.p);
+        HIP_TRY(c, hipGetLastError());
+        for (const auto& l : locals) {
+            hipLaunchKernelGGL(nwr::nwr_exc_place_kernel, dim3((unsigned)((l->n + 255) / 256)), dim3(256), 0, st,
+                               (const int64_t*)l->pos.p, (const uint8_t*)l->byte.p, l->n, (const uint32_t*)c->d_mask.p,
+                               (const uint32_t*)c->d_rsums.p, sum_exc, R->d_exc_pos.p, R->d_exc_byte.p);
+            HIP_TRY(c, hipGetLastError());
+        }
+        hipLaunchKernelGGL(nwr::nwr_exc_bounds_kernel, dim3((unsigned)((n_regions + 1 + 255) / 256)), dim3(256), 0, st,
+                           (const int64_t*)c->d_rpos.p, n_regions + 1, total, (const uint32_t*)c->d_mask.p,
+                           (const uint32_t*)c->d_rsums.p, sum_exc, c->d_gexc.p);
+        HIP_TRY(c, hipGetLastError());
+        HIP_TRY(c, hipEventRecord(c->ev[1], st));
+        int64_t in_mask = 0;
+        HIP_TRY(c, hipMemcpyAsync(&in_mask, c->d_ptotal.p, sizeof in_mask, hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipMemcpyAsync(R->gexc.data(), c->d_gexc.p, sizeof(int64_t) * (size_t)(n_regions + 1), hipMemcpyDeviceToHost, st));
+        HIP_TRY(c, hipEventRecord(R->ready, st));
+        HIP_TRY(c, hipStreamSynchronize(st));      // (the chunks' lists go out of scope)
+        HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+        R->pack_ms += ms;
+        if (in_mask != sum_exc) return fail(c, NW_E_STATE, "inconsistent exception mask");
+    } else {
+        HIP_TRY(c, hipEventRecord(R->ready, st));
+        HIP_TRY(c, hipStreamSynchronize(st));
+    }
+    R->n_exc = sum_exc;
+    return NW_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -836,7 +1297,8 @@ int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64
     if (!c) return NW_E_INVALID;
     if (!bam || !res) return fail(c, NW_E_INVALID, "null argument");
     std::memset(res, 0, sizeof *res);
-    if (flags & ~(NWR_BY_REFERENCE | NWR_EQX_AS_MATCH)) return fail(c, NW_E_INVALID, "unknown flags %d", (int)flags);
+    if (flags & ~(NWR_BY_REFERENCE | NWR_EQX_AS_MATCH | NWR_PACKED)) return fail(c, NW_E_INVALID, "unknown flags %d", (int)flags);
+    const bool packed = (flags & NWR_PACKED) != 0;
     const bool by_ref = (flags & NWR_BY_REFERENCE) != 0;
     if (by_ref) n_regions = (int64_t)bam->ref_len.size();
     if (n_regions < 0 || (!by_ref && n_regions > 0 && !regions)) return fail(c, NW_E_INVALID, "null regions");
@@ -847,6 +1309,11 @@ int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64
     R->region_off.assign((size_t)n_regions + 1, 0);
     res->n_regions = n_regions;
     res->handle = R;
+    if (packed) {      // (an empty result is a packed one all the same)
+        R->packed = true;
+        R->device = c->device;
+        R->gexc.assign((size_t)n_regions + 1, 0);
+    }
     if (n <= 0 || n_regions == 0) return NW_OK;
 
     auto bail = [&](int rc) {
@@ -892,15 +1359,18 @@ int nwr_extract(nwr_ctx* c, const nwr_bam* bam, const nwr_region* regions, int64
 
     std::vector<nwr::Hits> chunks;
     std::vector<int64_t> cursor((size_t)n_regions + 1);
+    std::vector<std::pair<int64_t, int64_t>> ranges;
     for (int64_t r0 = 0; r0 < n;) {
         const int64_t r1 = chunk_end(c, bam, r0, n);
         nwr::Hits h;
         rc = run_chunk(c, bam, r0, r1, a, perm, n_regions, &cursor, &h, &res->n_no_seq, &res->kernel_ms, &res->upload_ms);
         if (rc != NW_OK) return bail(rc);
         if (!h.reg.empty()) chunks.push_back(std::move(h));
+        ranges.emplace_back(r0, r1);
         r0 = r1;
     }
-    merge_chunks(chunks, n_regions, R);
+    merge_chunks(chunks, n_regions, R, packed);
+    if (packed && (rc = pack_result(c, bam, ranges, R, &res->upload_ms)) != NW_OK) return bail(rc);
     res->n_hits = (int64_t)R->h.reg.size();
     res->n_bytes = R->h.toff.back();
     return NW_OK;
@@ -910,7 +1380,8 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
     if (!c) return NW_E_INVALID;
     if (!bam || !res) return fail(c, NW_E_INVALID, "null argument");
     std::memset(res, 0, sizeof *res);
-    if (flags & ~NWR_EQX_AS_MATCH) return fail(c, NW_E_INVALID, "unknown flags %d", (int)flags);
+    if (flags & ~(NWR_EQX_AS_MATCH | NWR_PACKED)) return fail(c, NW_E_INVALID, "unknown flags %d", (int)flags);
+    const bool packed = (flags & NWR_PACKED) != 0;
     const int64_t n = (int64_t)bam->off.size() - 1;
     if (n > ((int64_t)1 << 30))
         return fail(c, NW_E_UNSUPPORTED, "%lld records: at most 2^30 in one nwr_discover call", (long long)n);
@@ -918,6 +1389,11 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
     R->discovered = true;
     R->region_off.assign(1, 0);
     res->handle = R;
+    if (packed) {
+        R->packed = true;
+        R->device = c->device;
+        R->gexc.assign(1, 0);
+    }
     if (n <= 0) return NW_OK;
     if (hipSetDevice(c->device) != hipSuccess) {
         delete R;
@@ -926,8 +1402,9 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
     }
 
     std::vector<nwr::Hits> chunks;
+    std::vector<std::pair<int64_t, int64_t>> ranges;
     int64_t n_regions = 0;
-    const int rc = [&]() -> int {
+    int rc = [&]() -> int {
         hipStream_t st = c->stream;
         // the table: a power of two of at least twice the records, so the load stays <= 1/2
         const grp::TableGeometry tg = grp::table_geometry(n, c->hash_bits);
@@ -949,7 +1426,6 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
         t.shift = tg.shift;
         t.hash_mask = tg.hash_mask;
 
-        std::vector<std::pair<int64_t, int64_t>> ranges;
         for (int64_t r0 = 0; r0 < n; r0 = ranges.back().second) ranges.emplace_back(r0, chunk_end(c, bam, r0, n));
         for (const auto& r : ranges) {
             const int rc1 = span_chunk(c, bam, r.first, r.second, flags, t, &res->kernel_ms, &res->upload_ms);
@@ -1043,12 +1519,15 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
         }
         return NW_OK;
     }();
+    if (rc == NW_OK) {
+        merge_chunks(chunks, n_regions, R, packed);
+        if (packed) rc = pack_result(c, bam, ranges, R, &res->upload_ms);
+    }
     if (rc != NW_OK) {
         delete R;
         res->handle = nullptr;
         return rc;
     }
-    merge_chunks(chunks, n_regions, R);
     res->n_regions = n_regions;
     res->n_hits = (int64_t)R->h.reg.size();
     res->n_bytes = R->h.toff.back();
@@ -1072,6 +1551,7 @@ int nwr_fetch(const nwr_result* res, int64_t* region_offsets, int64_t* src, int3
     const nwr::Result* R = (const nwr::Result*)res->handle;
     const nwr::Hits& h = R->h;
     const size_t nh = h.reg.size(), nb = (size_t)h.toff.back();
+    if (R->packed && (text || quals)) return NW_E_STATE;      // (a packed result holds neither)
     if (region_offsets) std::memcpy(region_offsets, R->region_off.data(), sizeof(int64_t) * R->region_off.size());
     if (src && nh) std::memcpy(src, h.src.data(), sizeof(int64_t) * nh);
     if (st && nh) std::memcpy(st, h.st.data(), sizeof(int32_t) * nh);
@@ -1080,6 +1560,66 @@ int nwr_fetch(const nwr_result* res, int64_t* region_offsets, int64_t* src, int3
     if (text && nb) std::memcpy(text, h.text.data(), nb);
     if (quals && nb) std::memcpy(quals, h.quals.data(), nb);
     return NW_OK;
+}
+
+int nwr_packed_info(const nwr_result* res, uint16_t* lens, int64_t* region_exc, int64_t* n_exc, float* kernel_ms) {
+    if (!res || !res->handle) return NW_E_INVALID;
+    const nwr::Result* R = (const nwr::Result*)res->handle;
+    if (!R->packed) return NW_E_STATE;
+    if (lens && !R->lens16.empty()) std::memcpy(lens, R->lens16.data(), sizeof(uint16_t) * R->lens16.size());
+    if (region_exc) std::memcpy(region_exc, R->gexc.data(), sizeof(int64_t) * R->gexc.size());
+    if (n_exc) *n_exc = R->n_exc;
+    if (kernel_ms) *kernel_ms = R->pack_ms;
+    return NW_OK;
+}
+
+int nwr_fetch_packed(const nwr_result* res, uint8_t* packed, int64_t cap, int64_t* exc_pos, uint8_t* exc_byte, int64_t* needed) {
+    if (!res || !res->handle) return NW_E_INVALID;
+    const nwr::Result* R = (const nwr::Result*)res->handle;
+    if (!R->packed) return NW_E_STATE;
+    const int64_t nbytes = (R->h.toff.back() + 3) / 4, ne = R->n_exc;
+    if (needed) *needed = nbytes;
+    if (cap < nbytes) return NW_E_CAPACITY;
+    if (nbytes == 0) return NW_OK;
+    if (hipSetDevice(R->device) != hipSuccess) return NW_E_HIP;
+    // (the packer has finished: nwr_extract and nwr_discover are synchronous)
+    if (packed && hipMemcpy(packed, R->d_words.p, (size_t)nbytes, hipMemcpyDeviceToHost) != hipSuccess) return NW_E_HIP;
+    if (exc_pos && ne > 0 && hipMemcpy(exc_pos, R->d_exc_pos.p, sizeof(int64_t) * (size_t)ne, hipMemcpyDeviceToHost) != hipSuccess)
+        return NW_E_HIP;
+    if (exc_byte && ne > 0 && hipMemcpy(exc_byte, R->d_exc_byte.p, (size_t)ne, hipMemcpyDeviceToHost) != hipSuccess)
+        return NW_E_HIP;
+    return NW_OK;
+}
+
+int nwr_adopt_region(const nwr_result* res, nw_ctx* ctx, int64_t g) {
+    if (!res || !res->handle || !ctx) return NW_E_INVALID;
+    nwr::Result* R = (nwr::Result*)res->handle;
+    if (!R->packed) return NW_E_STATE;
+    const int64_t n_regions = (int64_t)R->region_off.size() - 1;
+    if (g < 0 || g >= n_regions) return NW_E_INVALID;
+    const int64_t j0 = R->region_off[(size_t)g], m = R->region_off[(size_t)g + 1] - j0;
+    if (m <= 0) return NW_E_INVALID;      // (a region without hits has nothing to adopt)
+    int rc = nw_front::check_state(ctx);
+    if (rc != NW_OK) return rc;
+    if (nw_front::device_of(ctx) != R->device) return NW_E_INVALID;
+    if (hipSetDevice(R->device) != hipSuccess) return NW_E_HIP;
+    // every kLenGroup-th offset counted from the region's own first read
+    const int64_t ngroups = m / nw::kLenGroup + 1;
+    std::vector<int64_t> gb((size_t)ngroups);
+    for (int64_t q = 0; q < ngroups; ++q) gb[(size_t)q] = R->h.toff[(size_t)(j0 + q * nw::kLenGroup)];
+    if (R->d_gbase.reserve((size_t)ngroups) != hipSuccess) return NW_E_NOMEM;
+    if (hipMemcpy(R->d_gbase.p, gb.data(), sizeof(int64_t) * (size_t)ngroups, hipMemcpyHostToDevice) != hipSuccess) return NW_E_HIP;
+    const int64_t e0 = R->gexc[(size_t)g], ne = R->gexc[(size_t)g + 1] - e0;
+    // the whole call's stream and the region's slice of the exceptions, both in the call's
+    // coordinates: set_packed_batch copies bytes offsets[0] / 4 .. (offsets[m] + 3) / 4 of it
+    const nw_front::PackedSrc src{(const uint8_t*)R->d_words.p,
+                                  R->d_lens16.p + j0,
+                                  R->d_gbase.p,
+                                  ne > 0 ? R->d_exc_pos.p + e0 : nullptr,
+                                  ne > 0 ? R->d_exc_byte.p + e0 : nullptr,
+                                  true,
+                                  R->ready};
+    return nw_front::set_packed_batch(ctx, src, R->h.toff.data() + j0, R->lens16.data() + j0, m, ne);
 }
 
 void nwr_release(nwr_result* res) {

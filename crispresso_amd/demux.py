@@ -584,6 +584,64 @@ def check_summary_rows(rows: Sequence[dict]) -> List[str]:
     return [row["Amplicon_Sequence"] for row in rows]
 
 
+def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, what, min_identity_score, quant_kw,
+                      on_group) -> Dict[str, float]:
+    """The per-group body of :func:`summarize_pooled` and of
+    :func:`crispresso_amd.regions.summarize_regions`: for every ``g`` in ``keep``, in that order,
+    ``prepare(g)`` (the caller's ``set_reference`` and adoption: the group's reads become the
+    resident batch; returns their number, at most ``most``), one pass, ``nws_flags``, the quantifier on the
+    resident ops with the device ``pre`` (globals from ``rows[g]`` and ``quant_kw``),
+    ``nws_summary`` into ``out[g]``, the slot-15 check, ``on_group(g, aligner, n)``.  Errors name
+    the group as ``"<what> <Name>"``.  The aligner's output mode and the quantifier's module
+    globals are restored.  Returns the summed kernel times."""
+    import types
+
+    from . import quantify
+    from .devmem import DeviceBuffer
+
+    device = int(getattr(aligner, "device", 0))
+    times = {"flags": 0.0, "summary": 0.0, "quantify": 0.0}
+    mode = getattr(aligner, "output_mode", "rows")
+    saved_globals = quantify._GLOBALS
+    aligner.set_output("ops")
+    try:
+        with DeviceBuffer(most, device) as d_pre, DeviceBuffer(most, device) as d_keep, \
+                DeviceBuffer(16 * most, device) as d_out:
+            for g in keep:
+                amp, row = amplicons[g], rows[g]
+                n = prepare(g)
+                aligner.run_async()
+                aligner.sync()
+                dev = aligner.device_ops()
+                s.ensure_identity(min_identity_score, int(dev["max_cols"]))
+                try:
+                    s.flags(dev["stats"], n, d_pre.ptr, d_keep.ptr)
+                except SummaryError as exc:
+                    raise SummaryError(f"{what} {row['Name']}: {exc}", exc.code, exc.n_out_of_range) from None
+                args = types.SimpleNamespace(
+                    amplicon_seq=amp, guide_seq=row.get("sgRNA") or None, coding_seq=row.get("Coding_sequence") or None,
+                    expected_hdr_amplicon_seq=None, **quant_kw)
+                try:
+                    q.set_params(quantify.globals_from_args(args), args, amplicon_has_n="N" in amp.upper())
+                    q.run_device_ops(amp, dev, d_pre.ptr, n, d_out.ptr)
+                except quantify.QuantificationError as exc:     # (e.g. an amplicon too long for the quantifier's LDS)
+                    raise quantify.QuantificationError(f"{what} {row['Name']}: {exc}") from None
+                times["quantify"] += q.last_kernel_ms
+                out[g] = s.summary(d_out.ptr, d_pre.ptr, d_keep.ptr, n)
+                times["flags"] += s.flags_ms
+                times["summary"] += s.summary_ms
+                if int(out[g, 15]):
+                    raise quantify.QuantificationError(
+                        f"{what} {row['Name']}: {int(out[g, 15])} kept reads are not alignments of it "
+                        "(LEN_AMPLICON bases)")
+                if on_group is not None:
+                    on_group(g, aligner, n)
+    finally:
+        quantify._GLOBALS = saved_globals
+        aligner.set_output(mode)
+    return times
+
+
 def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1000, min_identity_score: float = 60.0,
                      window_around_sgrna: int = 1, cleavage_offset: int = -3, exclude_bp_from_left: int = 15,
                      exclude_bp_from_right: int = 15, ignore_substitutions: bool = False,
@@ -613,10 +671,7 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
     refused; the quantifier's effect vectors and histograms (not returned here) are not masked
     by the identity filter.  A kept read that is not an alignment of its amplicon (slot 15)
     raises :class:`crispresso_amd.quantify.QuantificationError`."""
-    import types
-
     from . import quantify
-    from .devmem import DeviceBuffer
     from .frontend import ResidentReads
 
     k, min_hits = check_params(k, min_hits)
@@ -654,52 +709,17 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
     keep = [g for g in range(len(amplicons)) if int(counts[g]) > min_reads]
     skipped = [g for g in range(len(amplicons)) if int(counts[g]) <= min_reads]
     out = np.zeros((len(amplicons), _lib.NWS_SLOTS), np.int64)
-    times = {"flags": 0.0, "summary": 0.0, "quantify": 0.0}
     most = max((int(counts[g]) for g in keep), default=0)
-    mode = getattr(aligner, "output_mode", "rows")
-    saved_globals = quantify._GLOBALS
-    aligner.set_output("ops")
-    try:
-        with DeviceBuffer(most, device) as d_pre, DeviceBuffer(most, device) as d_keep, \
-                DeviceBuffer(16 * most, device) as d_out:
-            for g in keep:
-                amp, row = amplicons[g], rows[g]
-                aligner.set_reference(amp)
-                n = d.adopt(aligner, g)
-                aligner.run_async()
-                aligner.sync()
-                dev = aligner.device_ops()
-                s.ensure_identity(min_identity_score, int(dev["max_cols"]))
-                try:
-                    s.flags(dev["stats"], n, d_pre.ptr, d_keep.ptr)
-                except SummaryError as exc:
-                    raise SummaryError(f"amplicon {row['Name']}: {exc}", exc.code, exc.n_out_of_range) from None
-                args = types.SimpleNamespace(
-                    amplicon_seq=amp, guide_seq=row.get("sgRNA") or None, coding_seq=row.get("Coding_sequence") or None,
-                    cleavage_offset=cleavage_offset, window_around_sgrna=window_around_sgrna,
-                    exclude_bp_from_left=exclude_bp_from_left, exclude_bp_from_right=exclude_bp_from_right,
-                    ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
-                    ignore_deletions=ignore_deletions,
-                    hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ,
-                    expected_hdr_amplicon_seq=None)
-                try:
-                    q.set_params(quantify.globals_from_args(args), args, amplicon_has_n="N" in amp.upper())
-                    q.run_device_ops(amp, dev, d_pre.ptr, n, d_out.ptr)
-                except quantify.QuantificationError as exc:     # (e.g. an amplicon too long for the quantifier's LDS)
-                    raise quantify.QuantificationError(f"amplicon {row['Name']}: {exc}") from None
-                times["quantify"] += q.last_kernel_ms
-                out[g] = s.summary(d_out.ptr, d_pre.ptr, d_keep.ptr, n)
-                times["flags"] += s.flags_ms
-                times["summary"] += s.summary_ms
-                if int(out[g, 15]):
-                    raise quantify.QuantificationError(
-                        f"amplicon {row['Name']}: {int(out[g, 15])} kept reads are not alignments of it "
-                        "(LEN_AMPLICON bases)")
-                if on_group is not None:
-                    on_group(g, aligner, n)
-    finally:
-        quantify._GLOBALS = saved_globals
-        aligner.set_output(mode)
+    def prepare(g: int) -> int:
+        aligner.set_reference(amplicons[g])
+        return d.adopt(aligner, g)
+
+    times = _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, "amplicon", min_identity_score,
+                              dict(window_around_sgrna=window_around_sgrna, cleavage_offset=cleavage_offset,
+                                   exclude_bp_from_left=exclude_bp_from_left, exclude_bp_from_right=exclude_bp_from_right,
+                                   ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
+                                   ignore_deletions=ignore_deletions,
+                                   hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ), on_group)
     frame = summary_frame([row["Name"] for row in rows], out, counts.tolist(), skipped)
     return PooledSummary(out, frame, res, skipped, times)
 

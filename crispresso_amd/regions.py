@@ -22,7 +22,13 @@ region's reads come back as the packed ``(buf, offsets)`` pair :func:`pooled.ali
 * :func:`discover_regions`   -- CRISPRessoPooled's genome mode (CRISPRessoPooledCORE.py:1045-1082):
   every distinct clip-extended span of the mapped records and its reads -> :class:`RegionReads`
 * :func:`region_sequences`   -- the genome's bases of such regions from a FASTA (host side)
-* ``python -m crispresso_amd.regions`` -- one ``.fastq.gz`` per target
+* :func:`extract_regions_resident`, :func:`demux_by_reference_resident`, :func:`discover_regions_resident`
+  -- the same calls with the reads left in HBM as the aligner's 2-bit batch (``NWR_PACKED``: packed
+  from the BAM's 4-bit codes, no text and no qualities anywhere) -> :class:`ResidentRegionReads`
+* :func:`align_regions_resident` -- every target's resident reads adopted by the aligner and aligned
+* :func:`summarize_regions`  -- CRISPRessoWGS / genome mode to SAMPLES_QUANTIFICATION_SUMMARY.txt in HBM;
+  its rows from :func:`read_wgs_region_file` + :func:`wgs_rows` or from :func:`discovered_rows`
+* ``python -m crispresso_amd.regions`` -- one ``.fastq.gz`` per target, or with ``--summary`` that table
 
 The reference's quirk is kept: ``=``, ``X``, ``H`` and ``P`` advance nothing in its walk
 (``eqx_as_match=True`` treats ``=`` and ``X`` as ``M``).  The one deliberate difference: a hit of
@@ -48,7 +54,11 @@ SEQ_CODES = "=ACMGRSVTWYHKDBN"
 
 
 class RegionsError(RuntimeError):
-    """A failed read or extraction."""
+    """A failed read or extraction; ``code`` is the library's return where there is one."""
+
+    def __init__(self, msg: str, code: int = 0):
+        super().__init__(msg)
+        self.code = code
 
 
 class _BamOwner:
@@ -344,6 +354,91 @@ class RegionReads:
         return sorted(range(len(keys)), key=keys.__getitem__)
 
 
+class ResidentRegionReads(RegionReads):
+    """The reads of every target of one ``NWR_PACKED`` call, 2-bit packed in HBM as the aligner's
+    batch (``include/crispr_regions.h``): everything a :class:`RegionReads` has except ``text``
+    and ``qual`` (both ``None``: no base and no quality reaches the host) and the methods that need
+    them, which raise :class:`RegionsError`.  Beside that: ``lens`` (uint16 per read),
+    ``region_exc`` (int64 ``[targets + 1]``: target ``g``'s slots of the exception list), ``n_exc``,
+    ``pack_ms`` (the packer's device time), :meth:`fetch_packed`, :meth:`adopt`, :meth:`close`.
+    A context manager; released at :meth:`close` or at garbage collection.  It stays valid after
+    the extractor that made it is closed."""
+
+    def __init__(self, lib, res, bam, names, region_off, src, st, en, toff, by_reference: bool):
+        super().__init__(bam, names, region_off, src, st, en, toff, None, None, int(res.n_no_seq), float(res.kernel_ms),
+                         float(res.upload_ms), by_reference)
+        self._lib, self._res = lib, res
+        self.lens = np.zeros(len(src), np.uint16)
+        self.region_exc = np.zeros(len(region_off), np.int64)
+        ne, ms = ctypes.c_int64(), ctypes.c_float()
+        rc = lib.nwr_packed_info(ctypes.byref(res), _lib.ptr(self.lens) if len(src) else None, _lib.ptr(self.region_exc),
+                                 ctypes.byref(ne), ctypes.byref(ms))
+        if rc != 0:
+            raise RegionsError(f"nwr_packed_info failed ({rc})")
+        self.n_exc, self.pack_ms = int(ne.value), float(ms.value)
+
+    @property
+    def closed(self) -> bool:
+        return self._res is None
+
+    def close(self) -> None:
+        if getattr(self, "_res", None) is not None:
+            self._lib.nwr_release(ctypes.byref(self._res))
+            self._res = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):  # pragma: no cover - runs at garbage collection
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if self._res is None:
+            raise RegionsError("the resident region reads were released")
+        return ctypes.byref(self._res)
+
+    def _no_text(self, what: str):
+        raise RegionsError(f"{what} needs the reads' bases on the host: these are resident in HBM (packed=True); "
+                           "run the call without it for text and qualities")
+
+    def reads(self, g: int):
+        self._no_text("reads()")
+
+    def quals(self, g: int):
+        self._no_text("quals()")
+
+    def _fields(self, g: int):
+        self._no_text("the FASTQ text")
+
+    def fetch_packed(self) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+        """(packed, exc_pos, exc_byte) of the whole call, copied to the host (for tests)."""
+        nbytes = (int(self.text_offsets[-1]) + 3) // 4
+        packed = np.zeros(max(nbytes, 1), np.uint8)
+        pos, byt = np.empty(self.n_exc, np.int64), np.empty(self.n_exc, np.uint8)
+        rc = self._lib.nwr_fetch_packed(self._live(), _lib.ptr(packed), nbytes, _lib.ptr(pos) if self.n_exc else None,
+                                        _lib.ptr(byt) if self.n_exc else None, None)
+        if rc != 0:
+            raise RegionsError(f"nwr_fetch_packed failed ({rc})")
+        return packed[:nbytes], pos, byt
+
+    def adopt(self, aligner, g: int) -> int:
+        """Make target ``g``'s reads the resident batch of ``aligner`` (ops output, its reference
+        set, on this device): ``nwr_adopt_region``.  Returns the target's number of reads."""
+        rc = self._lib.nwr_adopt_region(self._live(), aligner._h, int(g))
+        if rc != 0:
+            msg = aligner.lib.nw_last_error(aligner._h).decode(errors="replace")
+            raise RegionsError(f"nwr_adopt_region of target {g} failed ({rc}): the aligner says: {msg}", rc)
+        lo, hi = self._range(g)
+        aligner.adopted(None, self.text_offsets[lo:hi + 1])
+        return hi - lo
+
+
 class GpuRegionExtractor:
     """One ``nwr_ctx`` (one GPU).  Not thread-safe, like the aligner context."""
 
@@ -373,14 +468,21 @@ class GpuRegionExtractor:
         except Exception:
             pass
 
-    def extract(self, bam: BamRecords, table: Optional[np.ndarray], names: List[str], flags: int) -> RegionReads:
+    def extract(self, bam: BamRecords, table: Optional[np.ndarray], names: List[str], flags: int,
+                packed: bool = False) -> RegionReads:
+        """``nwr_extract``; ``packed=True`` adds ``NWR_PACKED`` and returns a
+        :class:`ResidentRegionReads`."""
         lib = self._lib
         res = _lib.NwrResult()
         n_reg = 0 if table is None else len(table)
+        if packed:
+            flags |= _lib.NWR_PACKED
         rc = lib.nwr_extract(self._ctx, bam._h, _lib.ptr(table) if n_reg else None, n_reg, flags, ctypes.byref(res))
         if rc != 0:
             msg = lib.nwr_last_error(self._ctx).decode(errors="replace")
-            raise RegionsError(f"nwr_extract failed ({rc}): {msg}")
+            raise RegionsError(f"nwr_extract failed ({rc}): {msg}", rc)
+        if flags & _lib.NWR_PACKED:
+            return self._resident(res, bam, names, bool(flags & _lib.NWR_BY_REFERENCE))
         try:
             arrays = self._fetch(res)
         finally:
@@ -388,37 +490,65 @@ class GpuRegionExtractor:
         return RegionReads(bam, names, *arrays, int(res.n_no_seq),
                            float(res.kernel_ms), float(res.upload_ms), bool(flags & _lib.NWR_BY_REFERENCE))
 
-    def _fetch(self, res):
+    def _fetch(self, res, with_text: bool = True):
         R, H, B = int(res.n_regions), int(res.n_hits), int(res.n_bytes)
         region_off = np.zeros(R + 1, np.int64)
         src, st, en = np.empty(H, np.int64), np.empty(H, np.int32), np.empty(H, np.int32)
-        toff, text, qual = np.zeros(H + 1, np.int64), np.empty(B, np.uint8), np.empty(B, np.uint8)
+        toff = np.zeros(H + 1, np.int64)
+        text, qual = (np.empty(B, np.uint8), np.empty(B, np.uint8)) if with_text else (None, None)
         rc = self._lib.nwr_fetch(ctypes.byref(res), _lib.ptr(region_off), _lib.ptr(src), _lib.ptr(st), _lib.ptr(en),
-                                 _lib.ptr(toff), _lib.ptr(text), _lib.ptr(qual))
+                                 _lib.ptr(toff), _lib.ptr(text) if with_text else None,
+                                 _lib.ptr(qual) if with_text else None)
         if rc != 0:
-            raise RegionsError(f"nwr_fetch failed ({rc})")
+            raise RegionsError(f"nwr_fetch failed ({rc})", rc)
         return region_off, src, st, en, toff, text, qual
 
-    def discover(self, bam: BamRecords, min_reads: int, flags: int) -> RegionReads:
+    def _resident_from(self, res, bam, names, arrays) -> "ResidentRegionReads":
+        try:
+            return ResidentRegionReads(self._lib, res, bam, names, *arrays[:5], True)
+        except Exception:
+            self._lib.nwr_release(ctypes.byref(res))
+            raise
+
+    def _resident(self, res, bam, names, by_reference: bool) -> "ResidentRegionReads":
+        """The index arrays of a packed result and the result itself, which stays in HBM."""
+        try:
+            return ResidentRegionReads(self._lib, res, bam, names, *self._fetch(res, False)[:5], by_reference)
+        except Exception:
+            self._lib.nwr_release(ctypes.byref(res))
+            raise
+
+    def discover(self, bam: BamRecords, min_reads: int, flags: int, packed: bool = False) -> RegionReads:
+        """``nwr_discover``; ``packed=True`` adds ``NWR_PACKED`` and returns a
+        :class:`ResidentRegionReads` with the same extra attributes."""
         lib = self._lib
         res = _lib.NwrResult()
+        if packed:
+            flags |= _lib.NWR_PACKED
+        packed = bool(flags & _lib.NWR_PACKED)
         rc = lib.nwr_discover(self._ctx, bam._h, flags, int(min_reads), ctypes.byref(res))
         if rc != 0:
             msg = lib.nwr_last_error(self._ctx).decode(errors="replace")
-            raise RegionsError(f"nwr_discover failed ({rc}): {msg}")
+            raise RegionsError(f"nwr_discover failed ({rc}): {msg}", rc)
+        done = False
         try:
-            arrays = self._fetch(res)
+            arrays = self._fetch(res, not packed)
             table = np.zeros(int(res.n_regions), REGION_DTYPE)
             n_records, stats = np.zeros(len(table), np.int64), np.zeros(4, np.int64)
             rc = lib.nwr_fetch_regions(ctypes.byref(res), _lib.ptr(table) if len(table) else None,
                                        _lib.ptr(n_records) if len(table) else None, _lib.ptr(stats))
             if rc != 0:
-                raise RegionsError(f"nwr_fetch_regions failed ({rc})")
+                raise RegionsError(f"nwr_fetch_regions failed ({rc})", rc)
+            done = True
         finally:
-            lib.nwr_release(ctypes.byref(res))
+            if not (packed and done):
+                lib.nwr_release(ctypes.byref(res))
         regs = [(bam.ref_names[int(r)], int(s), int(e)) for r, s, e in zip(table["ref_id"], table["bpstart"], table["bpend"])]
-        out = RegionReads(bam, ["REGION_%s_%d_%d" % r for r in regs], *arrays, int(res.n_no_seq), float(res.kernel_ms),
-                          float(res.upload_ms), True)
+        names = ["REGION_%s_%d_%d" % r for r in regs]
+        if packed:
+            out = self._resident_from(res, bam, names, arrays)
+        else:
+            out = RegionReads(bam, names, *arrays, int(res.n_no_seq), float(res.kernel_ms), float(res.upload_ms), True)
         out.regions, out.region_table, out.n_records = regs, table, n_records
         out.n_aligned, out.n_kept, out.n_emitted = int(stats[0]), int(stats[1]), int(stats[2])
         return out
@@ -498,6 +628,235 @@ def discover_regions(bam: BamRecords, min_reads: int = 0, eqx_as_match: bool = F
     return (extractor or default_extractor(device)).discover(bam, min_reads, flags)
 
 
+def extract_regions_resident(bam: BamRecords, regions: Union[str, Sequence[Region]], eqx_as_match: bool = False,
+                             device: int = 0, extractor: Optional[GpuRegionExtractor] = None) -> ResidentRegionReads:
+    """:func:`extract_regions` with the reads left in HBM as the aligner's packed batch
+    (``NWR_PACKED``): the same hits, no text and no qualities on the host."""
+    if isinstance(regions, str):
+        regions = read_region_file(regions)
+    table, names = region_table(bam, regions)
+    flags = _lib.NWR_EQX_AS_MATCH if eqx_as_match else 0
+    return (extractor or default_extractor(device)).extract(bam, table, names, flags, packed=True)
+
+
+def demux_by_reference_resident(bam: BamRecords, device: int = 0,
+                                extractor: Optional[GpuRegionExtractor] = None) -> ResidentRegionReads:
+    """:func:`demux_by_reference` with the reads left in HBM (``NWR_PACKED``)."""
+    return (extractor or default_extractor(device)).extract(bam, None, list(bam.ref_names), _lib.NWR_BY_REFERENCE,
+                                                            packed=True)
+
+
+def discover_regions_resident(bam: BamRecords, min_reads: int = 0, eqx_as_match: bool = False, device: int = 0,
+                              extractor: Optional[GpuRegionExtractor] = None) -> ResidentRegionReads:
+    """:func:`discover_regions` with the reads left in HBM (``NWR_PACKED``); ``regions``,
+    ``n_records`` and the other attributes of that call are the same."""
+    flags = _lib.NWR_EQX_AS_MATCH if eqx_as_match else 0
+    return (extractor or default_extractor(device)).discover(bam, min_reads, flags, packed=True)
+
+
+def align_regions_resident(region_reads: ResidentRegionReads, amplicons: Sequence[str], aligner, *, min_reads: int = 0,
+                           on_group=None):
+    """Align every target's resident reads to its amplicon where they lie: the counterpart of
+    :func:`crispresso_amd.demux.align_demultiplexed_resident` for BAM-fed reads.
+
+    For every target ``g`` with ``n_reads[g] >= max(min_reads, 1)``, in index order:
+    ``set_reference(amplicons[g])``, ``region_reads.adopt(aligner, g)`` (device to device), one
+    synchronised pass, ``on_group(g, aligner, n)`` while the group is resident, ``download_ops``.
+
+    Returns ``(ops_batches, skipped)``: one :class:`~crispresso_amd.aligner.OpsBatch` per target
+    (``None`` for a skipped one) and the skipped indices.  ``aligner`` must be on the reads'
+    device; its output mode is ops during the call and restored after."""
+    if len(amplicons) != len(region_reads):
+        raise ValueError(f"{len(amplicons)} amplicons for {len(region_reads)} targets")
+    bound = max(int(min_reads), 1)      # (a target without a read has nothing to adopt)
+    keep = [g for g in range(len(amplicons)) if int(region_reads.n_reads[g]) >= bound]
+    skipped = [g for g in range(len(amplicons)) if int(region_reads.n_reads[g]) < bound]
+    batches: list = [None] * len(amplicons)
+    mode = getattr(aligner, "output_mode", "rows")
+    aligner.set_output("ops")
+    try:
+        for g in keep:
+            aligner.set_reference(amplicons[g])
+            n = region_reads.adopt(aligner, g)
+            aligner.run_async()
+            aligner.sync()
+            if on_group is not None:
+                on_group(g, aligner, n)
+            batches[g] = aligner.download_ops(n)
+    finally:
+        aligner.set_output(mode)
+    return batches, skipped
+
+
+class RegionSummary:
+    """One :func:`summarize_regions` call: ``counts`` (int64 ``[regions, 16]``, ``nws_summary``'s
+    slots, zeros for a region that was not analysed), ``frame`` (the rows of
+    SAMPLES_QUANTIFICATION_SUMMARY.txt), ``skipped`` (the indices not analysed), ``kernel_ms``
+    (device ms of the flags, quantify and summary kernels, summed over the regions) and
+    ``n_reads`` (what ``Reads_total`` reports)."""
+
+    def __init__(self, counts, frame, skipped, kernel_ms, n_reads):
+        self.counts, self.frame, self.skipped, self.kernel_ms, self.n_reads = counts, frame, skipped, kernel_ms, n_reads
+
+
+def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, aligner, *, min_reads: int = 10,
+                      min_identity_score: float = 60.0, window_around_sgrna: int = 1, cleavage_offset: int = -3,
+                      exclude_bp_from_left: int = 15, exclude_bp_from_right: int = 15,
+                      ignore_substitutions: bool = False, ignore_insertions: bool = False,
+                      ignore_deletions: bool = False, hide_mutations_outside_window_NHEJ: bool = False, on_group=None,
+                      quantifier=None, summarizer=None) -> RegionSummary:
+    """A BAM's region reads to SAMPLES_QUANTIFICATION_SUMMARY.txt (CRISPRessoWGS, and
+    CRISPRessoPooled's genome mode) with the reads in HBM from the BAM's 4-bit codes to the 16
+    counters: what :func:`crispresso_amd.demux.summarize_pooled` is for amplicon mode.
+
+    ``region_reads``: a :class:`ResidentRegionReads` (:func:`extract_regions_resident`,
+    :func:`discover_regions_resident`); ``rows[g]`` describes its target ``g`` and needs ``Name``
+    and ``Amplicon_Sequence``, ``sgRNA`` and ``Coding_sequence`` are optional (:func:`wgs_rows`,
+    :func:`discovered_rows`).  ``aligner`` must be on the reads' device.  Per analysed region:
+    ``set_reference``, adoption (device to device), one pass, ``nws_flags``, the quantifier on the
+    resident ops, ``nws_summary``, ``on_group(g, aligner, n)``; only 16 integers come back.
+
+    The reference's rules that are kept:
+
+    * a region runs iff ``n_reads >= min_reads`` (CRISPRessoWGSCORE.py:721, default 10 at :304) --
+      not CRISPRessoPooled's strict ``>``; for genome mode pass ``min_reads`` as
+      :func:`discover_regions` explains;
+    * the amplicon is the region's sequence upper-cased and stripped (CRISPRessoCORE.py:1283);
+    * a row whose sequence is empty is not analysed and reports ``Reads_total`` 0 (WGSCORE:667);
+    * the sgRNA rules of WGSCORE:613-641 are :func:`wgs_rows`' business.
+
+    Deliberate differences: an ``Expected_HDR`` row is refused, as in ``summarize_pooled``; there
+    is no reverse-complement retry (BAM reads are in reference orientation); hits of records
+    without sequence or qualities are dropped (``n_no_seq``); a region without a read is never
+    analysed, whatever ``min_reads``.  Errors from the aligner (an amplicon it cannot take) and
+    from the quantifier (``MAX_QUANT_AMPLICON`` bases or more) name the region."""
+    from . import demux, quantify
+    from .aligner import NeedleError
+
+    if not isinstance(region_reads, ResidentRegionReads):
+        raise TypeError("summarize_regions takes the resident reads of a packed call (extract_regions_resident)")
+    if region_reads.closed:
+        raise ValueError("the resident region reads were released")
+    if len(rows) != len(region_reads):
+        raise ValueError(f"{len(rows)} rows for {len(region_reads)} regions")
+    amplicons = []
+    for row in rows:
+        amp = str(row.get("Amplicon_Sequence") or "").upper().strip()
+        if row.get("Expected_HDR"):
+            raise ValueError(f"region {row['Name']}: Expected_HDR is given, and dual alignment per region is not built")
+        if len(amp) >= demux.MAX_QUANT_AMPLICON:
+            raise ValueError(f"region {row['Name']} has {len(amp)} bases: fewer than {demux.MAX_QUANT_AMPLICON} are "
+                             "supported by the quantifier")
+        amplicons.append(amp)
+    device = int(getattr(aligner, "device", 0))
+    for what, stage in (("quantifier", quantifier), ("summarizer", summarizer)):
+        if stage is not None and int(stage.device) != device:
+            raise ValueError(f"the aligner is on device {device}, the {what} on device {stage.device}")
+    q = quantifier or quantify.default_quantifier(device)
+    s = summarizer or demux.default_summarizer(device)
+    n_reads = [int(n) if amp else 0 for n, amp in zip(region_reads.n_reads, amplicons)]
+    bound = max(int(min_reads), 1)
+    keep = [g for g in range(len(rows)) if n_reads[g] >= bound]
+    skipped = [g for g in range(len(rows)) if n_reads[g] < bound]
+    out = np.zeros((len(rows), _lib.NWS_SLOTS), np.int64)
+
+    def prepare(g: int) -> int:
+        try:
+            aligner.set_reference(amplicons[g])
+            return region_reads.adopt(aligner, g)
+        except NeedleError as exc:
+            raise NeedleError(f"region {rows[g]['Name']}: {exc}") from None
+        except RegionsError as exc:
+            raise RegionsError(f"region {rows[g]['Name']}: {exc}", exc.code) from None
+
+    times = demux._summarize_groups(
+        rows, amplicons, keep, max((n_reads[g] for g in keep), default=0), prepare, aligner, q, s, out, "region",
+        min_identity_score,
+        dict(window_around_sgrna=window_around_sgrna, cleavage_offset=cleavage_offset,
+             exclude_bp_from_left=exclude_bp_from_left, exclude_bp_from_right=exclude_bp_from_right,
+             ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
+             ignore_deletions=ignore_deletions, hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ),
+        on_group)
+    frame = demux.summary_frame([row["Name"] for row in rows], out, n_reads, skipped)
+    return RegionSummary(out, frame, skipped, times, n_reads)
+
+
+WGS_COLUMNS = ("chr_id", "bpstart", "bpend", "Name", "sgRNA", "Expected_HDR", "Coding_sequence")
+
+
+def read_wgs_region_file(path: str) -> List[dict]:
+    """The reference's region file with all its seven columns (WGSCORE:553-583) as dict rows:
+    ``chr_id bpstart bpend Name sgRNA Expected_HDR Coding_sequence``, tab-separated, ``#`` starts
+    a comment; missing trailing columns are ``""``, a missing name is ``chr_id_bpstart_bpend``, the
+    three sequences upper-cased (``capitalize_sequence``), spaces in a name ``_``.  Names that are
+    not all distinct raise, as in :func:`read_region_file`."""
+    out = []
+    with open(path) as f:
+        for line in f:
+            line = line.split("#", 1)[0].rstrip("\r\n")
+            if not line.strip():
+                continue
+            c = line.split("\t")
+            if len(c) < 3 or not c[0] or not c[1].strip() or not c[2].strip():
+                continue          # (the reference drops rows without the three columns)
+            c = (c + [""] * len(WGS_COLUMNS))[:len(WGS_COLUMNS)]
+            s, e = int(float(c[1])), int(float(c[2]))
+            name = c[3] if c[3] else "_".join(map(str, (c[0], s, e)))
+            out.append({"chr_id": c[0], "bpstart": s, "bpend": e, "Name": name, "sgRNA": c[4].upper(),
+                        "Expected_HDR": c[5].upper(), "Coding_sequence": c[6].upper()})
+    if len({r["Name"] for r in out}) != len(out):
+        raise ValueError("The amplicon names should be all distinct!")
+    for r in out:
+        r["Name"] = r["Name"].replace(" ", "_")
+    return out
+
+
+def _reverse_complement(seq: str) -> str:
+    return seq.translate(str.maketrans("ACGTNacgtn", "TGCANtgcan"))[::-1]
+
+
+def checked_guides(sgrna: str, sequence: str) -> str:
+    """The sgRNA column after the reference's check (WGSCORE:613-641): every comma-separated
+    guide, stripped and upper-cased, must hold only ``ACGTN`` (else ``ValueError``, the
+    reference's ``find_wrong_nt`` exception); the column is kept as it is when one of the guides
+    or its reverse complement occurs in ``sequence``, else it is ``""``.  The reference searches the
+    sequence as ``faidx`` printed it, before its upper-casing, and so does this."""
+    if not sgrna:
+        return ""
+    found = False
+    for guide in sgrna.strip().upper().split(","):
+        wrong = sorted(set(guide) - set("ATCGN"))
+        if wrong:
+            raise ValueError("The sgRNA sequence %s contains wrong characters:%s" % (guide, " ".join(wrong)))
+        if guide and (guide in sequence or _reverse_complement(guide) in sequence):
+            found = True
+    return sgrna if found else ""
+
+
+def wgs_rows(region_rows: Sequence[dict], fasta_path: str) -> List[dict]:
+    """The rows :func:`summarize_regions` takes from those of :func:`read_wgs_region_file`: each
+    region's sequence from the FASTA (:func:`region_sequences`), upper-cased and stripped as
+    ``Amplicon_Sequence`` (CRISPRessoCORE.py:1283; empty for a region outside its contig), the
+    sgRNA through :func:`checked_guides`; the other columns as they are."""
+    seqs = region_sequences(fasta_path, [(r["chr_id"], r["bpstart"], r["bpend"]) for r in region_rows])
+    out = []
+    for r, seq in zip(region_rows, seqs):
+        row = dict(r)
+        row["sgRNA"] = checked_guides(r.get("sgRNA") or "", seq)
+        row["Amplicon_Sequence"] = seq.upper().strip()
+        out.append(row)
+    return out
+
+
+def discovered_rows(region_reads: RegionReads, fasta_path: str) -> List[dict]:
+    """Rows for genome mode from a :func:`discover_regions` result: ``Name`` is
+    ``REGION_<chr>_<bpstart>_<bpend>``, the sequence from the FASTA, no guide."""
+    seqs = region_sequences(fasta_path, region_reads.regions)
+    return [{"chr_id": c, "bpstart": s, "bpend": e, "Name": name, "sgRNA": "", "Expected_HDR": "", "Coding_sequence": "",
+             "Amplicon_Sequence": seq.upper().strip()}
+            for name, (c, s, e), seq in zip(region_reads.target_names, region_reads.regions, seqs)]
+
+
 def _fasta_index(fasta_path: str) -> Dict[str, Tuple[int, int, int, int]]:
     """name -> (length, offset of the first base, bases per line, bytes per line): the ``.fai``
     beside the file when there is one, else one pass over the file."""
@@ -558,6 +917,32 @@ def region_sequences(fasta_path: str, regions: Sequence[Region]) -> List[str]:
     return out
 
 
+def _summary_main(args, bam: BamRecords) -> int:
+    """``--summary``: SAMPLES_QUANTIFICATION_SUMMARY.txt of the regions of a file (CRISPRessoWGS;
+    --min-reads defaults to its 10) or of the discovered ones (genome mode: --min-reads as given)."""
+    import os
+
+    from . import demux
+    from .aligner import GpuAligner
+
+    if args.discover:
+        res = discover_regions_resident(bam, args.min_reads, args.eqx_as_match, args.device)
+        rows, min_reads = discovered_rows(res, args.genome), args.min_reads
+    else:
+        region_rows = read_wgs_region_file(args.regions)
+        rows = wgs_rows(region_rows, args.genome)
+        res = extract_regions_resident(bam, [(r["chr_id"], r["bpstart"], r["bpend"], r["Name"]) for r in region_rows],
+                                       args.eqx_as_match, args.device)
+        min_reads = args.min_reads or 10
+    os.makedirs(args.out, exist_ok=True)
+    with res, GpuAligner(args.device) as aligner:
+        summary = summarize_regions(rows, res, aligner, min_reads=min_reads)
+    demux.write_summary(os.path.join(args.out, "SAMPLES_QUANTIFICATION_SUMMARY.txt"), summary.frame)
+    for row, n in zip(rows, summary.n_reads):
+        print(f"{row['Name']}\t{n}")
+    return 0
+
+
 def main(argv=None) -> int:
     import argparse
     import os
@@ -572,13 +957,21 @@ def main(argv=None) -> int:
                    help="one read set per distinct clip-extended span of the mapped records (CRISPRessoPooled's genome mode)")
     p.add_argument("--eqx-as-match", action="store_true", help="treat the CIGAR operations = and X as M")
     p.add_argument("--min-reads", type=int, default=0, help="with --discover: write only regions with at least N reads")
-    p.add_argument("--genome", help="with --discover: a plain FASTA; regions.tsv gets the regions' sequences")
+    p.add_argument("--genome", help="a plain FASTA: with --discover regions.tsv gets the regions' sequences; "
+                                    "with --summary the regions' amplicons")
+    p.add_argument("--summary", action="store_true",
+                   help="with --regions or --discover, and --genome: align and quantify every region in HBM and write "
+                        "SAMPLES_QUANTIFICATION_SUMMARY.txt; no FASTQ is written, the bases never reach the host")
     p.add_argument("--reference-order", action="store_true",
                    help="with --discover: reads in the order the reference's sort leaves them (C locale)")
     p.add_argument("--out", required=True, help="output directory")
     p.add_argument("--device", type=int, default=0)
     args = p.parse_args(argv)
-    if not args.discover and (args.min_reads or args.genome or args.reference_order):
+    if args.summary and not args.genome:
+        p.error("--summary needs --genome, the regions' amplicons come from it")
+    if args.summary and (args.by_reference or args.reference_order):
+        p.error("--summary goes with --regions or --discover, and not with --reference-order")
+    if not args.discover and not args.summary and (args.min_reads or args.genome or args.reference_order):
         p.error("--min-reads, --genome and --reference-order go with --discover")
     if args.min_reads < 0:
         p.error("--min-reads must not be negative")
@@ -586,6 +979,8 @@ def main(argv=None) -> int:
         if f and not os.path.exists(f):
             p.error(f"cannot open {f}")
     bam = read_bam(args.bam)
+    if args.summary:
+        return _summary_main(args, bam)
     if args.discover:
         res = discover_regions(bam, args.min_reads, args.eqx_as_match, args.device)
         os.makedirs(args.out, exist_ok=True)

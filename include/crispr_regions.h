@@ -29,6 +29,23 @@
  * stored + 33.  The result is a function of the input alone.  More than 65535 CIGAR ops (the CG
  * tag) are not looked up: the record is walked by the ops of its core CIGAR.  The binding is
  * crispresso_amd/regions.py (ctypes).  Error codes are the NW_E_* of include/crispr_nw.h.
+ *
+ * NWR_PACKED (nwr_extract and nwr_discover; combines freely with the other flags): the reads stay
+ * in HBM as the aligner's batch.  Hits, st / en, region order, n_no_seq, n_hits, n_bytes and
+ * nwr_fetch_regions with its stats are exactly what the same call without the flag gives; no
+ * ASCII base and no quality is written to HBM or copied to the host, and nwr_fetch with a
+ * non-NULL text or quals is NW_E_STATE (its other arrays are served as before).  The result owns,
+ * in HBM and until nwr_release, what nw_pack_reads (include/crispr_nw.h) makes of the text /
+ * text_offsets of the unflagged call, made straight from the BAM's 4-bit codes:
+ *   the stream      base i in bits 2 (i % 4) of byte i / 4, A C T G = 0 1 2 3 (BAM codes 1 2 8 4),
+ *                   defined up to byte (n_bytes + 3) / 4, bits past the end 0;
+ *   the exceptions  ascending by position: every base whose BAM code is not 1, 2, 4 or 8, its byte
+ *                   the upper-case letter of "=MRSVWYHKDBN", 0 bits in the stream;
+ *   lens            uint16 per hit.
+ * The order is the result's own: region-major, record order within a region, across all chunks
+ * of the call.  A hit longer than 65535 bases, or 2^32 or more bases in the call, is
+ * NW_E_UNSUPPORTED (the message names the record or the count).  The result stays valid after
+ * nwr_destroy of the context that made it, and the context may run further calls while it lives.
  */
 #ifndef CRISPR_REGIONS_H
 #define CRISPR_REGIONS_H
@@ -45,6 +62,7 @@ typedef struct nwr_bam nwr_bam;
 #define NWR_MAX_REGIONS (1 << 20)
 #define NWR_BY_REFERENCE 1
 #define NWR_EQX_AS_MATCH 2
+#define NWR_PACKED 4
 
 typedef struct nwr_region {
     int64_t bpstart, bpend; /* 1-based, as in SAM text and the reference's region file */
@@ -145,6 +163,28 @@ int nwr_discover(nwr_ctx* c, const nwr_bam* bam, int32_t flags, int64_t min_read
  * (records with flag & 0x904 == 0, the reference's get_n_aligned_bam), the kept records, the
  * emitted regions, 0 (reserved).  Any pointer may be NULL. */
 int nwr_fetch_regions(const nwr_result* res, nwr_region* regions, int64_t* n_records, int64_t stats[4]);
+
+/* The packed batch of a result made with NWR_PACKED (NW_E_STATE on any other): lens uint16
+ * [n_hits], region_exc int64 [n_regions + 1] (region g's exceptions are the slots region_exc[g] ..
+ * region_exc[g + 1] of the list), their number, the packer's device time.  Any pointer may be
+ * NULL. */
+int nwr_packed_info(const nwr_result* res, uint16_t* lens, int64_t* region_exc, int64_t* n_exc, float* kernel_ms);
+
+/* Copies the batch to the host (for tests): the (n_bytes + 3) / 4 bytes of the stream to packed
+ * (cap bytes; *needed gets the size, NW_E_CAPACITY and nothing copied when cap is short), the
+ * exception list to exc_pos / exc_byte (n_exc each).  Any pointer may be NULL. */
+int nwr_fetch_packed(const nwr_result* res, uint8_t* packed, int64_t cap, int64_t* exc_pos, uint8_t* exc_byte, int64_t* needed);
+
+/* Makes region g's reads the resident batch of the aligner context ctx, as nw_batch_upload_packed
+ * of the same reads would: a device-to-device adoption of the region's slice on ctx's stream,
+ * behind the packer's event; only the group-base offsets cross PCIe.  ctx needs a reference and
+ * NW_OUT_OPS, else NW_E_STATE, as on a result made without NWR_PACKED; NW_E_INVALID for a context
+ * on another device, g out of range or a region without hits.  A refusal changes nothing;
+ * regions are adoptable in any order, any number of times.  A region whose hits are all empty
+ * reads is adoptable: its records come out NW_FLAG_EMPTY.  The aligner's own errors are read with
+ * nw_last_error(ctx). */
+struct nw_ctx;
+int nwr_adopt_region(const nwr_result* res, struct nw_ctx* ctx, int64_t g);
 
 #ifdef __cplusplus
 }
