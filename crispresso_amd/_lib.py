@@ -79,7 +79,9 @@ DEMUX_EXPORTS = (
 NWD_NO_HIT, NWD_TIE = -1, -2
 
 # Every symbol include/crispr_summary.h declares.
-SUMMARY_EXPORTS = ("nws_create", "nws_destroy", "nws_last_error", "nws_set_identity", "nws_flags", "nws_summary")
+SUMMARY_EXPORTS = ("nws_create", "nws_destroy", "nws_last_error", "nws_set_identity", "nws_flags", "nws_summary",
+                   "nws_set_printed", "nws_printed", "nws_flags_dual")
+NWS_NO_TENTHS = 0xFFFF          # nws_printed's value for a record without a printed identity
 NWS_SLOTS = 16
 # The slots of nws_summary's output, in order (the enum of include/crispr_summary.h).
 NWS_SLOT_NAMES = ("n", "n_total", "n_unmodified", "n_modified", "n_repaired", "n_mixed_hdr_nhej",
@@ -362,6 +364,10 @@ def load() -> ctypes.CDLL:
         "nws_set_identity": (c_int, [ctx_p, c_void_p, c_void_p, c_int32]),
         "nws_flags": (c_int, [ctx_p, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_float)]),
         "nws_summary": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_float)]),
+        "nws_set_printed": (c_int, [ctx_p, c_void_p, c_int32, c_int32]),
+        "nws_printed": (c_int, [ctx_p, c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_float)]),
+        "nws_flags_dual": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64),
+                                   POINTER(c_float)]),
         "nwr_read_bam": (c_int, [c_char_p, c_void_p, c_int64, POINTER(c_void_p), c_char_p, c_int64]),
         "nwr_bam_free": (None, [c_void_p]),
         "nwr_bam_count": (c_int64, [c_void_p]),

@@ -1,9 +1,10 @@
 // nw_summary.hip -- the end of the pooled amplicon mode on a resident group (gfx950): the
-// identity filter and the UNMODIFIED flag from the aligner's records, and the 16 counters of
-// SAMPLES_QUANTIFICATION_SUMMARY.txt from the quantifier's per-read results, behind the C ABI of
-// include/crispr_summary.h.  Nothing per read crosses PCIe.
+// identity filter and the UNMODIFIED flag from the aligner's records (for a row with an
+// Expected_HDR amplicon: from the records of both passes, with the HDR and MIXED flags), and the
+// 16 counters of SAMPLES_QUANTIFICATION_SUMMARY.txt from the quantifier's per-read results, behind
+// the C ABI of include/crispr_summary.h.  Nothing per read crosses PCIe.
 //
-// Both kernels run on the context's stream:
+// The kernels run on the context's stream:
 //   flags    one lane per nw_stat record (two 16-byte loads).  keep and pre are two compares of
 //            n_ident with the threshold tables at aln_len; the tables are the host's (the printed
 //            "%.1f" identity is never redone here).  An aln_len outside the tables is counted:
@@ -14,6 +15,13 @@
 //            wavefronts' sums meet in LDS and lanes 0..14 add the block's non-zero sums to the
 //            counters, one 64-bit integer atomic per counter per block.  Integer sums: the result
 //            does not depend on the order of arrival.
+//   printed  one lane per nw_stat record: the PRINTED identity float("%.1f" % (100 n_ident /
+//            aln_len)) in tenths, as a uint16.  t, r = divmod(1000 n_ident, aln_len) in 32-bit
+//            integers; t + 1 when 2 r > aln_len; on a rounding midpoint (2 r == aln_len, rare)
+//            one bit of the host's 1000-bit table, 128 bytes in HBM, read only then.
+//   dual     one lane per read of a row with an Expected_HDR amplicon: the ref record's tenths by
+//            the same function, the HDR pass's stored tenths, then CORE:1849-1856, 536-548 and
+//            2014 as integer compares.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -52,6 +60,92 @@ __global__ __launch_bounds__(kBlk) void nws_flags_kernel(const FlagArgs a) {
         if (!outside) {
             keep = !(flags & NW_FLAG_EMPTY) && n_ident >= a.keep_min[aln_len];
             pre = n_ident >= a.unmod_min[aln_len] ? NWQ_PRE_UNMODIFIED : 0;
+        }
+        a.keep[r] = keep;
+        a.pre[r] = pre;
+    }
+    const unsigned long long ob = __ballot(outside);
+    if (lane == 0 && ob) atomicAdd(a.bad, (unsigned long long)__popcll(ob));
+}
+
+// The printed identity of n_ident / aln_len in tenths (0 .. 1000): what "%.1f" prints of the
+// double 100.0 * n_ident / aln_len.  0 < aln_len <= NWS_MAX_COLS and 0 <= n_ident <= aln_len, so
+// 1000 n_ident < 2^30.  Away from a midpoint the rational lies at least 1 / (20 aln_len) from it
+// and the double's error (about 1e-14) cannot move it across; on a midpoint the double is the
+// correctly rounded (2 t + 1) / 20, whose printing depends on t alone: tie_up's bit t.
+__device__ __forceinline__ uint32_t printed_tenths(uint32_t n_ident, uint32_t aln_len, const uint32_t* tie_up) {
+    const uint32_t x = 1000u * n_ident;
+    uint32_t t = x / aln_len;
+    const uint32_t r2 = 2u * (x - t * aln_len);
+    if (r2 > aln_len) {
+        ++t;
+    } else if (r2 == aln_len) {         // (t <= 999 here: r > 0)
+        t += (tie_up[t >> 5] >> (t & 31)) & 1u;
+    }
+    return t;
+}
+
+// One record's tenths: kNoTenths for an EMPTY record, `outside` set (and kNoTenths) for one whose
+// aln_len or n_ident is out of range, 0 for aln_len == 0 (as aligner.printed_percent).
+constexpr uint32_t kNoTenths = 0xFFFFu;
+
+__device__ __forceinline__ uint32_t record_tenths(const int4* stats, int64_t r, const uint32_t* tie_up, bool& empty,
+                                                  bool& outside) {
+    const int4 lo = stats[2 * r], hi = stats[2 * r + 1];
+    const int32_t aln_len = lo.x, n_ident = lo.y;
+    empty = (hi.w & NW_FLAG_EMPTY) != 0;
+    outside = aln_len < 0 || aln_len > NWS_MAX_COLS || n_ident < 0 || n_ident > aln_len;
+    if (outside) return kNoTenths;
+    return aln_len == 0 ? 0u : printed_tenths((uint32_t)n_ident, (uint32_t)aln_len, tie_up);
+}
+
+struct PrintedArgs {
+    const int4* stats;          // [2 n]
+    int64_t n;
+    const uint32_t* tie_up;     // [32]: 1000 bits
+    uint16_t* tenths;           // [n]
+    unsigned long long* bad;    // [1]
+};
+
+__global__ __launch_bounds__(kBlk) void nws_printed_kernel(const PrintedArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    bool outside = false;
+    if (r < a.n) {
+        bool empty;
+        const uint32_t t = record_tenths(a.stats, r, a.tie_up, empty, outside);
+        a.tenths[r] = (uint16_t)(empty ? kNoTenths : t);
+    }
+    const unsigned long long ob = __ballot(outside);
+    if (lane == 0 && ob) atomicAdd(a.bad, (unsigned long long)__popcll(ob));
+}
+
+struct DualArgs {
+    const int4* stats;          // [2 n]: the records of the pass against the amplicon
+    const uint16_t* rep;        // [n]: nws_printed of the pass against the Expected_HDR amplicon
+    int64_t n;
+    const uint32_t* tie_up;
+    uint32_t keep_tenths, hdr_tenths;
+    uint8_t* pre;
+    uint8_t* keep;
+    unsigned long long* bad;
+};
+
+__global__ __launch_bounds__(kBlk) void nws_flags_dual_kernel(const DualArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    bool outside = false;
+    if (r < a.n) {
+        bool empty;
+        const uint32_t ref = record_tenths(a.stats, r, a.tie_up, empty, outside);
+        const uint32_t rep = a.rep[r];
+        const bool has_rep = rep <= 1000u;          // kNoTenths: no repaired score, every test on it is false
+        outside = outside || (!has_rep && rep != kNoTenths);
+        uint8_t keep = 0, pre = 0;
+        if (!outside) {
+            keep = !empty && (ref >= a.keep_tenths || (has_rep && rep >= a.keep_tenths));
+            if (ref == 1000u) pre = NWQ_PRE_UNMODIFIED;
+            if (has_rep && ref < rep) pre |= rep >= a.hdr_tenths ? NWQ_PRE_HDR : NWQ_PRE_MIXED;
         }
         a.keep[r] = keep;
         a.pre[r] = pre;
@@ -117,7 +211,24 @@ struct nws_ctx : hd::DevContext {
     int32_t max_cols = -1;         // -1: no tables yet
     hd::DevBuf<int32_t> d_keep_min, d_unmod_min;
     hd::DevBuf<unsigned long long> d_counters;
+    bool printed = false;          // nws_set_printed succeeded
+    hd::DevBuf<uint32_t> d_tie_up; // [32]
+    int32_t keep_tenths = 0, hdr_tenths = 0;
 };
+
+// The shared tail of the one-lane-per-record calls: the bad-record count back, the kernel's time.
+static int finish_counted(nws_ctx* c, int64_t* n_bad, float* kernel_ms, unsigned long long* bad) {
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[1], st));
+    HIP_TRY(c, hipMemcpyAsync(bad, c->d_counters.p, sizeof *bad, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    if (kernel_ms) *kernel_ms = ms;
+    if (n_bad) *n_bad = (int64_t)*bad;
+    return NW_OK;
+}
 
 using hd::fail;
 
@@ -182,6 +293,93 @@ int nws_flags(nws_ctx* c, const void* d_stats, int64_t n, uint8_t* d_pre, uint8_
     if (n_out_of_range) *n_out_of_range = (int64_t)bad;
     if (bad)
         return fail(c, NW_E_INVALID, "%llu records with an alignment length outside [0, %d]", bad, (int)c->max_cols);
+    return NW_OK;
+}
+
+int nws_set_printed(nws_ctx* c, const uint8_t* tie_up, int32_t keep_tenths, int32_t hdr_tenths) {
+    if (!c) return NW_E_INVALID;
+    if (!tie_up) return fail(c, NW_E_INVALID, "null table");
+    if (keep_tenths < 0 || keep_tenths > 1001 || hdr_tenths < 0 || hdr_tenths > 1001)
+        return fail(c, NW_E_INVALID, "thresholds %d and %d: tenths from 0 to 1001", (int)keep_tenths, (int)hdr_tenths);
+    uint32_t bits[32] = {};
+    for (int t = 0; t < 1000; ++t) {
+        if (tie_up[t] > 1) return fail(c, NW_E_INVALID, "tie_up[%d] = %d: 0 or 1", t, (int)tie_up[t]);
+        bits[t >> 5] |= (uint32_t)tie_up[t] << (t & 31);
+    }
+    c->printed = false;             // no tables until this call succeeds
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->d_tie_up.reserve(32));
+    HIP_TRY(c, hipMemcpyAsync(c->d_tie_up.p, bits, sizeof bits, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    c->keep_tenths = keep_tenths;
+    c->hdr_tenths = hdr_tenths;
+    c->printed = true;
+    return NW_OK;
+}
+
+int nws_printed(nws_ctx* c, const void* d_stats, int64_t n, uint16_t* d_tenths, int64_t* n_out_of_range,
+                float* kernel_ms) {
+    if (!c) return NW_E_INVALID;
+    if (n_out_of_range) *n_out_of_range = 0;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (!c->printed) return fail(c, NW_E_STATE, "nws_printed before nws_set_printed");
+    if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "record count %lld out of range", (long long)n);
+    if (n == 0) return NW_OK;
+    if (!d_stats || !d_tenths) return fail(c, NW_E_INVALID, "null device array");
+    if ((uintptr_t)d_stats % 16) return fail(c, NW_E_INVALID, "the records are not 16-byte aligned");
+    if ((uintptr_t)d_tenths % 2) return fail(c, NW_E_INVALID, "the tenths are not 2-byte aligned");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, c->d_counters.reserve(NWS_SLOTS));
+    HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(unsigned long long), st));
+    nws::PrintedArgs a{};
+    a.stats = (const int4*)d_stats;
+    a.n = n;
+    a.tie_up = c->d_tie_up.p;
+    a.tenths = d_tenths;
+    a.bad = c->d_counters.p;
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(nws::nws_printed_kernel, dim3((unsigned)((n + nws::kBlk - 1) / nws::kBlk)), dim3(nws::kBlk), 0, st, a);
+    unsigned long long bad = 0;
+    if (int rc = finish_counted(c, n_out_of_range, kernel_ms, &bad)) return rc;
+    if (bad)
+        return fail(c, NW_E_INVALID, "%llu records with an alignment length outside [0, %d] or identities outside it",
+                    bad, NWS_MAX_COLS);
+    return NW_OK;
+}
+
+int nws_flags_dual(nws_ctx* c, const void* d_stats_ref, const uint16_t* d_tenths_rep, int64_t n, uint8_t* d_pre,
+                   uint8_t* d_keep, int64_t* n_out_of_range, float* kernel_ms) {
+    if (!c) return NW_E_INVALID;
+    if (n_out_of_range) *n_out_of_range = 0;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (!c->printed) return fail(c, NW_E_STATE, "nws_flags_dual before nws_set_printed");
+    if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "record count %lld out of range", (long long)n);
+    if (n == 0) return NW_OK;
+    if (!d_stats_ref || !d_tenths_rep || !d_pre || !d_keep) return fail(c, NW_E_INVALID, "null device array");
+    if ((uintptr_t)d_stats_ref % 16) return fail(c, NW_E_INVALID, "the records are not 16-byte aligned");
+    if ((uintptr_t)d_tenths_rep % 2) return fail(c, NW_E_INVALID, "the tenths are not 2-byte aligned");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, c->d_counters.reserve(NWS_SLOTS));
+    HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(unsigned long long), st));
+    nws::DualArgs a{};
+    a.stats = (const int4*)d_stats_ref;
+    a.rep = d_tenths_rep;
+    a.n = n;
+    a.tie_up = c->d_tie_up.p;
+    a.keep_tenths = (uint32_t)c->keep_tenths;
+    a.hdr_tenths = (uint32_t)c->hdr_tenths;
+    a.pre = d_pre;
+    a.keep = d_keep;
+    a.bad = c->d_counters.p;
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(nws::nws_flags_dual_kernel, dim3((unsigned)((n + nws::kBlk - 1) / nws::kBlk)), dim3(nws::kBlk), 0, st,
+                       a);
+    unsigned long long bad = 0;
+    if (int rc = finish_counted(c, n_out_of_range, kernel_ms, &bad)) return rc;
+    if (bad)
+        return fail(c, NW_E_INVALID, "%llu reads with a record or stored tenths out of range", bad);
     return NW_OK;
 }
 

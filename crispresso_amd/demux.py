@@ -14,11 +14,12 @@ as no hit, not guessed.
   adopted by the aligner where it lies; only decisions, records and runs cross PCIe
 * :func:`summarize_pooled` -- raw reads (host, or merged pairs resident in HBM) to the reference's
   ``SAMPLES_QUANTIFICATION_SUMMARY.txt``: the identity filter and the counts on the device
-  (``include/crispr_summary.h``, crispresso_amd/csrc/nw_summary.hip), 16 integers back per amplicon
+  (``include/crispr_summary.h``, crispresso_amd/csrc/nw_summary.hip), 16 integers back per amplicon;
+  with ``allow_hdr`` the rows' ``Expected_HDR`` amplicons by a second alignment per group
 * :func:`read_amplicons_file` -- the reference's tab-separated amplicon table
 * ``python -m crispresso_amd.demux`` -- FASTQ (``-r2``: pairs) + amplicon table -> per-amplicon
-  FASTQ files, the reference's ``REPORT_READS_ALIGNED_TO_AMPLICONS.txt`` and, with ``--summary``,
-  the summary table
+  FASTQ files, the reference's ``REPORT_READS_ALIGNED_TO_AMPLICONS.txt`` and, with ``--summary``
+  (``--hdr``: the ``Expected_HDR`` column used), the summary table
 
 Every refusal is made here, before any GPU call.  There is no CPU fallback.
 """
@@ -448,6 +449,34 @@ def identity_thresholds(min_identity_score: float, max_cols: int, start: int = 0
     return keep_min, unmod_min
 
 
+def printed_tables(min_identity_score: float, threshold: float = 98.0) -> Tuple[np.ndarray, int, int]:
+    """The host values ``nws_set_printed`` takes, ``(tie_up, keep_tenths, hdr_tenths)``:
+
+    * ``tie_up`` uint8 [1000]: ``tie_up[t]`` is 1 iff an identity on the rounding midpoint between
+      ``t`` and ``t + 1`` tenths prints ``t + 1``.  There ``100.0 * n / L`` is the correctly rounded
+      double of ``(2 t + 1) / 20`` whatever ``n`` and ``L`` are, so ``printed_percent(2 t + 1, 2000)``
+      decides for all of them;
+    * ``keep_tenths``: the smallest ``t`` in 0..1000 with ``t / 10.0 > min_identity_score``
+      (CRISPRessoCORE.py:1849-1852), 1001 if none;
+    * ``hdr_tenths``: the smallest ``t`` with ``t / 10.0 >= threshold`` (CORE:536-548), 1001 if none.
+
+    ``float("%.1f" % x)`` is ``t / 10.0`` for the ``t`` it prints, so comparing tenths is comparing
+    what the reference compares."""
+    from .aligner import printed_percent
+
+    tie_up = np.zeros(1000, np.uint8)
+    for t in range(1000):
+        v = printed_percent(2 * t + 1, 2000)
+        if v == (t + 1) / 10.0:
+            tie_up[t] = 1
+        elif v != t / 10.0:
+            raise AssertionError(f"the midpoint above {t} tenths prints {v!r}")
+    score, bound = float(min_identity_score), float(threshold)
+    keep_tenths = next((t for t in range(1001) if t / 10.0 > score), 1001)
+    hdr_tenths = next((t for t in range(1001) if t / 10.0 >= bound), 1001)
+    return tie_up, keep_tenths, hdr_tenths
+
+
 class GpuSummarizer:
     """One ``nws_ctx`` (one GPU): the flags and the 16 counters of a resident group
     (``include/crispr_summary.h``).  Not thread-safe."""
@@ -463,6 +492,8 @@ class GpuSummarizer:
         self.min_identity_score: Optional[float] = None
         self.keep_min = self.unmod_min = np.zeros(0, np.int32)
         self.flags_ms = self.summary_ms = 0.0
+        self.printed_key: Optional[Tuple[float, float]] = None     # (min_identity_score, threshold) of set_printed
+        self.printed_ms = 0.0
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):
@@ -516,6 +547,39 @@ class GpuSummarizer:
         self.flags_ms = float(ms.value)
         self._check(rc, "nws_flags", int(bad.value))
 
+    def set_printed(self, tie_up: np.ndarray, keep_tenths: int, hdr_tenths: int) -> None:
+        """``nws_set_printed``: the values of :func:`printed_tables`."""
+        tie_up = np.ascontiguousarray(tie_up, np.uint8)
+        if tie_up.shape != (1000,):
+            raise ValueError("tie_up must hold 1000 values")
+        self.printed_key = None
+        self._check(self._lib.nws_set_printed(self._ctx, _lib.ptr(tie_up), int(keep_tenths), int(hdr_tenths)),
+                    "nws_set_printed")
+
+    def ensure_printed(self, min_identity_score: float, threshold: float) -> None:
+        """The printed-identity values for this score and threshold, built once."""
+        key = (float(min_identity_score), float(threshold))
+        if self.printed_key != key:
+            self.set_printed(*printed_tables(*key))
+            self.printed_key = key
+
+    def printed(self, d_stats: int, n: int, d_tenths: int) -> None:
+        """``nws_printed``: n nw_stat records in, their printed identities in tenths (uint16 [n])
+        out.  A record out of range raises :class:`SummaryError` with their number."""
+        bad, ms = ctypes.c_int64(), ctypes.c_float()
+        rc = self._lib.nws_printed(self._ctx, d_stats, n, d_tenths, ctypes.byref(bad), ctypes.byref(ms))
+        self.printed_ms = float(ms.value)
+        self._check(rc, "nws_printed", int(bad.value))
+
+    def flags_dual(self, d_stats_ref: int, d_tenths_rep: int, n: int, d_pre: int, d_keep: int) -> None:
+        """``nws_flags_dual``: the amplicon pass's records and the Expected_HDR pass's tenths in,
+        pre (UNMODIFIED, HDR, MIXED) and keep (uint8 [n]) out."""
+        bad, ms = ctypes.c_int64(), ctypes.c_float()
+        rc = self._lib.nws_flags_dual(self._ctx, d_stats_ref, d_tenths_rep, n, d_pre, d_keep, ctypes.byref(bad),
+                                      ctypes.byref(ms))
+        self.flags_ms = float(ms.value)
+        self._check(rc, "nws_flags_dual", int(bad.value))
+
     def summary(self, d_reads: int, d_pre: int, d_keep: int, n: int) -> np.ndarray:
         """``nws_summary``: the 16 slots (int64) of n nwq_read records on the device."""
         out = np.zeros(_lib.NWS_SLOTS, np.int64)
@@ -544,7 +608,8 @@ class PooledSummary:
     frame: "object"                    # pandas.DataFrame: SAMPLES_QUANTIFICATION_SUMMARY.txt's rows
     result: DemuxResult
     skipped: List[int]
-    kernel_ms: Dict[str, float]        # device ms of the flags and summary kernels, summed over the groups
+    kernel_ms: Dict[str, float]        # device ms of the flags, summary, quantify and printed kernels, summed over the
+                                       # groups, and hdr_pass: the host's wall ms of the Expected_HDR passes
 
 
 def summary_frame(names: Sequence[str], counts: np.ndarray, n_reads: Sequence[int], skipped: Sequence[int]):
@@ -572,12 +637,39 @@ def write_summary(path: str, frame) -> None:
     frame.fillna("NA").to_csv(path, sep="\t", index=None)
 
 
-def check_summary_rows(rows: Sequence[dict]) -> List[str]:
+MAX_ALIGNER_REFERENCE = 8192        # nw_set_reference's limit (include/crispr_nw.h)
+
+
+def checked_expected_hdr(row: dict, amplicon: str, what: str = "amplicon") -> Optional[str]:
+    """The row's ``Expected_HDR`` after the reference's checks (CRISPRessoCORE.py:1349-1364):
+    stripped and upper-cased; ``None`` when empty.  Equal to the amplicon, a byte outside
+    ``ATCGN`` or more bases than the aligner takes raise ``ValueError`` naming the row.  The
+    reference's ``pairwise2.globalxx`` identity of the two (CORE:1366-1382) is not checked."""
+    hdr = str(row.get("Expected_HDR") or "").strip().upper()
+    if not hdr:
+        return None
+    if hdr == amplicon:
+        raise ValueError(f"{what} {row['Name']}: the amplicon sequence expected after an HDR and the reference "
+                         "amplicon cannot be the same")
+    wrong = sorted(set(hdr) - set("ATCGN"))
+    if wrong:
+        raise ValueError(f"{what} {row['Name']}: the amplicon sequence expected after an HDR contains wrong "
+                         "characters:%s" % " ".join(wrong))
+    if len(hdr) > MAX_ALIGNER_REFERENCE:
+        raise ValueError(f"{what} {row['Name']}: Expected_HDR has {len(hdr)} bases: at most {MAX_ALIGNER_REFERENCE} "
+                         "are supported by the aligner")
+    return hdr
+
+
+def check_summary_rows(rows: Sequence[dict], allow_hdr: bool = False) -> List[str]:
     """The refusals :func:`summarize_pooled` makes on the amplicon table, before any GPU call;
-    returns the amplicon sequences."""
+    returns the amplicon sequences.  An ``Expected_HDR`` row is refused unless ``allow_hdr``, and
+    with it goes through :func:`checked_expected_hdr`."""
     for row in rows:
         if row.get("Expected_HDR"):
-            raise ValueError(f"amplicon {row['Name']}: Expected_HDR is given, and dual alignment per amplicon is not built")
+            if not allow_hdr:
+                raise ValueError(f"amplicon {row['Name']}: Expected_HDR is given, and dual alignment per amplicon is not built")
+            checked_expected_hdr(row, row["Amplicon_Sequence"])
         if len(row["Amplicon_Sequence"]) >= MAX_QUANT_AMPLICON:
             raise ValueError(f"amplicon {row['Name']} has {len(row['Amplicon_Sequence'])} bases: fewer than "
                              f"{MAX_QUANT_AMPLICON} are supported")
@@ -585,42 +677,64 @@ def check_summary_rows(rows: Sequence[dict]) -> List[str]:
 
 
 def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, what, min_identity_score, quant_kw,
-                      on_group) -> Dict[str, float]:
+                      on_group, hdrs=None, hdr_threshold: float = 98.0) -> Dict[str, float]:
     """The per-group body of :func:`summarize_pooled` and of
     :func:`crispresso_amd.regions.summarize_regions`: for every ``g`` in ``keep``, in that order,
-    ``prepare(g)`` (the caller's ``set_reference`` and adoption: the group's reads become the
-    resident batch; returns their number, at most ``most``), one pass, ``nws_flags``, the quantifier on the
-    resident ops with the device ``pre`` (globals from ``rows[g]`` and ``quant_kw``),
-    ``nws_summary`` into ``out[g]``, the slot-15 check, ``on_group(g, aligner, n)``.  Errors name
-    the group as ``"<what> <Name>"``.  The aligner's output mode and the quantifier's module
-    globals are restored.  Returns the summed kernel times."""
+    ``prepare(g, amplicons[g])`` (the caller's ``set_reference`` and adoption: the group's reads
+    become the resident batch; returns their number, at most ``most``), one pass, ``nws_flags``,
+    the quantifier on the resident ops with the device ``pre`` (globals from ``rows[g]`` and
+    ``quant_kw``), ``nws_summary`` into ``out[g]``, the slot-15 check, ``on_group(g, aligner, n)``.
+
+    A group with ``hdrs[g]`` (its checked Expected_HDR amplicon) is first prepared with that as
+    the reference and aligned, and ``nws_printed`` keeps two bytes per read of that pass; then the
+    body above runs with ``nws_flags_dual`` in place of ``nws_flags``.  The Expected_HDR pass goes
+    first, so the ops the quantifier and ``on_group`` see are the amplicon pass's.
+
+    Errors name the group as ``"<what> <Name>"``.  The aligner's output mode and the quantifier's
+    module globals are restored.  Returns the summed kernel times (``flags``, ``summary``,
+    ``quantify``, ``printed``) and ``hdr_pass``, the host's wall ms of the Expected_HDR passes."""
+    import time
     import types
 
     from . import quantify
     from .devmem import DeviceBuffer
 
     device = int(getattr(aligner, "device", 0))
-    times = {"flags": 0.0, "summary": 0.0, "quantify": 0.0}
+    times = {"flags": 0.0, "summary": 0.0, "quantify": 0.0, "printed": 0.0, "hdr_pass": 0.0}
     mode = getattr(aligner, "output_mode", "rows")
     saved_globals = quantify._GLOBALS
+    hdrs = hdrs or [None] * len(rows)
+    most_hdr = max((2 * most for g in keep if hdrs[g]), default=0)
     aligner.set_output("ops")
     try:
         with DeviceBuffer(most, device) as d_pre, DeviceBuffer(most, device) as d_keep, \
-                DeviceBuffer(16 * most, device) as d_out:
+                DeviceBuffer(16 * most, device) as d_out, DeviceBuffer(most_hdr, device) as d_rep:
             for g in keep:
-                amp, row = amplicons[g], rows[g]
-                n = prepare(g)
-                aligner.run_async()
-                aligner.sync()
-                dev = aligner.device_ops()
-                s.ensure_identity(min_identity_score, int(dev["max_cols"]))
+                amp, row, hdr = amplicons[g], rows[g], hdrs[g]
                 try:
-                    s.flags(dev["stats"], n, d_pre.ptr, d_keep.ptr)
+                    if hdr:
+                        t0 = time.perf_counter()
+                        n = prepare(g, hdr)
+                        aligner.run_async()
+                        aligner.sync()
+                        s.ensure_printed(min_identity_score, hdr_threshold)
+                        s.printed(aligner.device_ops()["stats"], n, d_rep.ptr)
+                        times["printed"] += s.printed_ms
+                        times["hdr_pass"] += (time.perf_counter() - t0) * 1e3
+                    n = prepare(g, amp)
+                    aligner.run_async()
+                    aligner.sync()
+                    dev = aligner.device_ops()
+                    if hdr:
+                        s.flags_dual(dev["stats"], d_rep.ptr, n, d_pre.ptr, d_keep.ptr)
+                    else:
+                        s.ensure_identity(min_identity_score, int(dev["max_cols"]))
+                        s.flags(dev["stats"], n, d_pre.ptr, d_keep.ptr)
                 except SummaryError as exc:
                     raise SummaryError(f"{what} {row['Name']}: {exc}", exc.code, exc.n_out_of_range) from None
                 args = types.SimpleNamespace(
                     amplicon_seq=amp, guide_seq=row.get("sgRNA") or None, coding_seq=row.get("Coding_sequence") or None,
-                    expected_hdr_amplicon_seq=None, **quant_kw)
+                    expected_hdr_amplicon_seq=hdr, hdr_perfect_alignment_threshold=hdr_threshold, **quant_kw)
                 try:
                     q.set_params(quantify.globals_from_args(args), args, amplicon_has_n="N" in amp.upper())
                     q.run_device_ops(amp, dev, d_pre.ptr, n, d_out.ptr)
@@ -648,7 +762,8 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
                      ignore_insertions: bool = False, ignore_deletions: bool = False,
                      hide_mutations_outside_window_NHEJ: bool = False, k: int = 16, min_hits: int = 2,
                      both_strands: bool = True, on_group=None, demultiplexer: Optional[GpuDemultiplexer] = None,
-                     quantifier=None, summarizer: Optional[GpuSummarizer] = None) -> PooledSummary:
+                     quantifier=None, summarizer: Optional[GpuSummarizer] = None, allow_hdr: bool = False,
+                     hdr_perfect_alignment_threshold: float = 98.0) -> PooledSummary:
     """Raw reads to CRISPRessoPooled's SAMPLES_QUANTIFICATION_SUMMARY.txt (amplicon mode) with the
     reads in HBM from the first kernel to the last.
 
@@ -666,16 +781,28 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
     :func:`crispresso_amd.quantify.globals_from_args`); ``nws_summary``; ``on_group(g, aligner,
     n)`` while the group is resident.  Per group only 16 integers come back.
 
+    With ``allow_hdr`` a row's ``Expected_HDR`` (checked by :func:`checked_expected_hdr`) is used
+    as the reference does with ``-e`` (CRISPRessoCORE.py:1849-1856, 536-548, 2014): the group is
+    adopted and aligned twice, first against the Expected_HDR amplicon, of which ``nws_printed``
+    keeps the printed identity (two bytes a read), then against the amplicon; ``nws_flags_dual``
+    keeps a read whose printed identity to either is above ``min_identity_score`` and marks it
+    HDR (repaired above ref and >= ``hdr_perfect_alignment_threshold``) or MIXED (above ref,
+    below the threshold); the quantifier runs on the alignment to the amplicon.  Rows without
+    ``Expected_HDR`` go the way described above in the same call.  The demultiplexer's index
+    holds the amplicons only: an HDR allele's read reaches its amplicon through the windows
+    outside the edit.
+
     Differences from the reference, deliberate: a read is aligned in the orientation the
     demultiplexer chose and is not retried reverse-complemented; an ``Expected_HDR`` row is
-    refused; the quantifier's effect vectors and histograms (not returned here) are not masked
-    by the identity filter.  A kept read that is not an alignment of its amplicon (slot 15)
-    raises :class:`crispresso_amd.quantify.QuantificationError`."""
+    refused unless ``allow_hdr``; the quantifier's effect vectors and histograms (not returned
+    here) are not masked by the identity filter.  A kept read that is not an alignment of its
+    amplicon (slot 15) raises :class:`crispresso_amd.quantify.QuantificationError`."""
     from . import quantify
     from .frontend import ResidentReads
 
     k, min_hits = check_params(k, min_hits)
-    amplicons = check_summary_rows(rows)
+    amplicons = check_summary_rows(rows, allow_hdr)
+    hdrs = [checked_expected_hdr(row, amp) for row, amp in zip(rows, amplicons)] if allow_hdr else None
     abuf, aoff = pack_amplicons(amplicons)
     device = int(getattr(aligner, "device", 0))
     resident = isinstance(reads, ResidentReads)
@@ -710,8 +837,8 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
     skipped = [g for g in range(len(amplicons)) if int(counts[g]) <= min_reads]
     out = np.zeros((len(amplicons), _lib.NWS_SLOTS), np.int64)
     most = max((int(counts[g]) for g in keep), default=0)
-    def prepare(g: int) -> int:
-        aligner.set_reference(amplicons[g])
+    def prepare(g: int, reference: str) -> int:
+        aligner.set_reference(reference)
         return d.adopt(aligner, g)
 
     times = _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, "amplicon", min_identity_score,
@@ -719,7 +846,8 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
                                    exclude_bp_from_left=exclude_bp_from_left, exclude_bp_from_right=exclude_bp_from_right,
                                    ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
                                    ignore_deletions=ignore_deletions,
-                                   hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ), on_group)
+                                   hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ), on_group,
+                              hdrs, float(hdr_perfect_alignment_threshold))
     frame = summary_frame([row["Name"] for row in rows], out, counts.tolist(), skipped)
     return PooledSummary(out, frame, res, skipped, times)
 
@@ -808,7 +936,8 @@ def _resident_fastq(rows, fastq, fastq_r2, device, k, min_hits, both_strands, mi
     from .aligner import GpuAligner
     from .frontend import prepare_fastq_resident
 
-    amplicons = check_summary_rows(rows) if summary is not None else [r["Amplicon_Sequence"] for r in rows]
+    amplicons = (check_summary_rows(rows, bool(summary.get("allow_hdr"))) if summary is not None
+                 else [r["Amplicon_Sequence"] for r in rows])
     with GpuAligner(device) as al:
         al.set_reference(amplicons[0])          # the front end wants one; any amplicon will do
         rr, _ = prepare_fastq_resident(al, fastq, fastq_r2, with_quals=True, **front)
@@ -912,6 +1041,12 @@ def build_parser():
     g.add_argument("--min_identity_score", type=float, default=60.0)
     g.add_argument("--window_around_sgrna", type=int, default=1)
     g.add_argument("--cleavage_offset", type=int, default=-3)
+    g.add_argument("--hdr", action="store_true",
+                   help="use the table's Expected_HDR column: align every read to it as well and report HDR%% and "
+                        "Mixed_HDR-NHEJ%% (without this option a table with the column filled is refused)")
+    g.add_argument("--hdr_perfect_alignment_threshold", type=float, default=None,
+                   help="with --hdr: the printed identity to the Expected_HDR amplicon from which a read is HDR and "
+                        "not mixed (default 98.0)")
     return p
 
 
@@ -948,6 +1083,14 @@ def options_from_args(p, args) -> dict:
                              cleavage_offset=args.cleavage_offset)
     elif (args.min_identity_score, args.window_around_sgrna, args.cleavage_offset) != (60.0, 1, -3):
         p.error("--min_identity_score, --window_around_sgrna and --cleavage_offset are used only with --summary")
+    if args.hdr:
+        if not args.summary:
+            p.error("--hdr is used only with --summary")
+        kw["summary"]["allow_hdr"] = True
+        kw["summary"]["hdr_perfect_alignment_threshold"] = (
+            98.0 if args.hdr_perfect_alignment_threshold is None else args.hdr_perfect_alignment_threshold)
+    elif args.hdr_perfect_alignment_threshold is not None:
+        p.error("--hdr_perfect_alignment_threshold is used only with --hdr")
     return kw
 
 
@@ -961,7 +1104,7 @@ def main(argv=None) -> int:
     kw = options_from_args(p, args)
     if "summary" in kw:
         try:
-            check_summary_rows(read_amplicons_file(args.amplicons_file))
+            check_summary_rows(read_amplicons_file(args.amplicons_file), bool(kw["summary"].get("allow_hdr")))
         except ValueError as exc:
             p.error(str(exc))
     out = demultiplex_fastq(args.amplicons_file, args.fastq_r1, args.output_folder, **kw)

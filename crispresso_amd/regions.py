@@ -704,7 +704,8 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
                       exclude_bp_from_left: int = 15, exclude_bp_from_right: int = 15,
                       ignore_substitutions: bool = False, ignore_insertions: bool = False,
                       ignore_deletions: bool = False, hide_mutations_outside_window_NHEJ: bool = False, on_group=None,
-                      quantifier=None, summarizer=None) -> RegionSummary:
+                      quantifier=None, summarizer=None, allow_hdr: bool = False,
+                      hdr_perfect_alignment_threshold: float = 98.0) -> RegionSummary:
     """A BAM's region reads to SAMPLES_QUANTIFICATION_SUMMARY.txt (CRISPRessoWGS, and
     CRISPRessoPooled's genome mode) with the reads in HBM from the BAM's 4-bit codes to the 16
     counters: what :func:`crispresso_amd.demux.summarize_pooled` is for amplicon mode.
@@ -725,7 +726,14 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
     * a row whose sequence is empty is not analysed and reports ``Reads_total`` 0 (WGSCORE:667);
     * the sgRNA rules of WGSCORE:613-641 are :func:`wgs_rows`' business.
 
-    Deliberate differences: an ``Expected_HDR`` row is refused, as in ``summarize_pooled``; there
+    With ``allow_hdr`` a row's ``Expected_HDR`` (the region file's sixth column; checked by
+    :func:`crispresso_amd.demux.checked_expected_hdr`) is used as the reference does with ``-e``:
+    the region is adopted and aligned twice, ``nws_printed`` keeps the printed identity to the
+    Expected_HDR amplicon and ``nws_flags_dual`` applies the reference's rule on the two printed
+    identities with ``hdr_perfect_alignment_threshold``, as ``summarize_pooled`` explains.
+
+    Deliberate differences: an ``Expected_HDR`` row is refused unless ``allow_hdr``, as in
+    ``summarize_pooled``; discovered regions carry no ``Expected_HDR``; there
     is no reverse-complement retry (BAM reads are in reference orientation); hits of records
     without sequence or qualities are dropped (``n_no_seq``); a region without a read is never
     analysed, whatever ``min_reads``.  Errors from the aligner (an amplicon it cannot take) and
@@ -739,11 +747,12 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
         raise ValueError("the resident region reads were released")
     if len(rows) != len(region_reads):
         raise ValueError(f"{len(rows)} rows for {len(region_reads)} regions")
-    amplicons = []
+    amplicons, hdrs = [], []
     for row in rows:
         amp = str(row.get("Amplicon_Sequence") or "").upper().strip()
-        if row.get("Expected_HDR"):
+        if row.get("Expected_HDR") and not allow_hdr:
             raise ValueError(f"region {row['Name']}: Expected_HDR is given, and dual alignment per region is not built")
+        hdrs.append(demux.checked_expected_hdr(row, amp, "region") if allow_hdr and amp else None)
         if len(amp) >= demux.MAX_QUANT_AMPLICON:
             raise ValueError(f"region {row['Name']} has {len(amp)} bases: fewer than {demux.MAX_QUANT_AMPLICON} are "
                              "supported by the quantifier")
@@ -760,9 +769,9 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
     skipped = [g for g in range(len(rows)) if n_reads[g] < bound]
     out = np.zeros((len(rows), _lib.NWS_SLOTS), np.int64)
 
-    def prepare(g: int) -> int:
+    def prepare(g: int, reference: str) -> int:
         try:
-            aligner.set_reference(amplicons[g])
+            aligner.set_reference(reference)
             return region_reads.adopt(aligner, g)
         except NeedleError as exc:
             raise NeedleError(f"region {rows[g]['Name']}: {exc}") from None
@@ -776,7 +785,7 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
              exclude_bp_from_left=exclude_bp_from_left, exclude_bp_from_right=exclude_bp_from_right,
              ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
              ignore_deletions=ignore_deletions, hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ),
-        on_group)
+        on_group, hdrs if allow_hdr else None, float(hdr_perfect_alignment_threshold))
     frame = demux.summary_frame([row["Name"] for row in rows], out, n_reads, skipped)
     return RegionSummary(out, frame, skipped, times, n_reads)
 
@@ -917,7 +926,7 @@ def region_sequences(fasta_path: str, regions: Sequence[Region]) -> List[str]:
     return out
 
 
-def _summary_main(args, bam: BamRecords) -> int:
+def _summary_main(args, bam: BamRecords, hdr_options: dict) -> int:
     """``--summary``: SAMPLES_QUANTIFICATION_SUMMARY.txt of the regions of a file (CRISPRessoWGS;
     --min-reads defaults to its 10) or of the discovered ones (genome mode: --min-reads as given)."""
     import os
@@ -936,16 +945,15 @@ def _summary_main(args, bam: BamRecords) -> int:
         min_reads = args.min_reads or 10
     os.makedirs(args.out, exist_ok=True)
     with res, GpuAligner(args.device) as aligner:
-        summary = summarize_regions(rows, res, aligner, min_reads=min_reads)
+        summary = summarize_regions(rows, res, aligner, min_reads=min_reads, **hdr_options)
     demux.write_summary(os.path.join(args.out, "SAMPLES_QUANTIFICATION_SUMMARY.txt"), summary.frame)
     for row, n in zip(rows, summary.n_reads):
         print(f"{row['Name']}\t{n}")
     return 0
 
 
-def main(argv=None) -> int:
+def build_parser():
     import argparse
-    import os
 
     p = argparse.ArgumentParser(prog="python -m crispresso_amd.regions",
                                 description="The reads of every target region or reference of a BAM, one .fastq.gz each")
@@ -966,7 +974,35 @@ def main(argv=None) -> int:
                    help="with --discover: reads in the order the reference's sort leaves them (C locale)")
     p.add_argument("--out", required=True, help="output directory")
     p.add_argument("--device", type=int, default=0)
+    p.add_argument("--hdr", action="store_true",
+                   help="with --summary: use the region file's Expected_HDR column (align every read to it as well and "
+                        "report HDR%% and Mixed_HDR-NHEJ%%); without this option a file with the column filled is refused")
+    p.add_argument("--hdr_perfect_alignment_threshold", type=float, default=None,
+                   help="with --hdr: the printed identity to the Expected_HDR amplicon from which a read is HDR and not "
+                        "mixed (default 98.0)")
+    return p
+
+
+def summary_options(p, args) -> dict:
+    """The keyword arguments ``--hdr`` and ``--hdr_perfect_alignment_threshold`` add to the
+    ``--summary`` call of :func:`summarize_regions`: none without ``--hdr``.  A usage error
+    (``p.error``) for ``--hdr`` without ``--summary`` and for the threshold without ``--hdr``."""
+    if args.hdr:
+        if not args.summary:
+            p.error("--hdr is used only with --summary")
+        return {"allow_hdr": True, "hdr_perfect_alignment_threshold":
+                98.0 if args.hdr_perfect_alignment_threshold is None else args.hdr_perfect_alignment_threshold}
+    if args.hdr_perfect_alignment_threshold is not None:
+        p.error("--hdr_perfect_alignment_threshold is used only with --hdr")
+    return {}
+
+
+def main(argv=None) -> int:
+    import os
+
+    p = build_parser()
     args = p.parse_args(argv)
+    hdr_options = summary_options(p, args)
     if args.summary and not args.genome:
         p.error("--summary needs --genome, the regions' amplicons come from it")
     if args.summary and (args.by_reference or args.reference_order):
@@ -980,7 +1016,7 @@ def main(argv=None) -> int:
             p.error(f"cannot open {f}")
     bam = read_bam(args.bam)
     if args.summary:
-        return _summary_main(args, bam)
+        return _summary_main(args, bam, hdr_options)
     if args.discover:
         res = discover_regions(bam, args.min_reads, args.eqx_as_match, args.device)
         os.makedirs(args.out, exist_ok=True)

@@ -14,6 +14,8 @@
  * indexed by aln_len (crispresso_amd.demux.identity_thresholds):
  *   keep_min[L]  = the smallest n_ident whose printed identity is > min_identity_score, L + 1 if none;
  *   unmod_min[L] = the smallest n_ident that prints 100.0, L + 1 if none.
+ * A row with an Expected_HDR amplicon compares two printed identities of different aln_len; for
+ * it nws_printed and nws_flags_dual compute the printed value in tenths by integers (below).
  *
  * The binding is crispresso_amd/demux.py (ctypes).  Error codes are the NW_E_* of crispr_nw.h.
  */
@@ -78,6 +80,45 @@ int nws_flags(nws_ctx* c, const void* d_stats, int64_t n, uint8_t* d_pre, uint8_
  * kernel_ms may be NULL.  Synchronous. */
 int nws_summary(nws_ctx* c, const void* d_reads, const uint8_t* d_pre, const uint8_t* d_keep, int64_t n, int64_t* out,
                 float* kernel_ms);
+
+/* ---- rows with an Expected_HDR amplicon: two printed identities per read ----------------------
+ *
+ * For such a row every read is aligned to the amplicon and to the Expected_HDR amplicon, and the
+ * reference tests score_ref and score_repaired, both PRINTED (CORE:1849-1856, 536-548, 2014).  Their
+ * alignment lengths differ, so thresholds on n_ident per aln_len do not do; the device computes the
+ * printed value itself, in tenths, without formatting a float:
+ *   t, r = divmod(1000 n_ident, aln_len); tenths = t when 2 r < aln_len, t + 1 when 2 r > aln_len,
+ *   and t + tie_up[t] on a rounding midpoint (2 r == aln_len), where the double is the correctly
+ *   rounded (2 t + 1) / 20 and what "%.1f" makes of it depends on t alone.
+ * aln_len == 0 prints 0.  crispresso_amd.demux.printed_tables builds the host values.
+ *
+ * nws_set_printed: tie_up HOST uint8 [1000] of 0 / 1 (kept as 128 bytes of bits on the device),
+ * keep_tenths = the smallest tenths whose value is > min_identity_score, hdr_tenths = the smallest
+ * whose value is >= hdr_perfect_alignment_threshold, both in [0, 1001] (1001: none), else
+ * NW_E_INVALID.  Replaces the previous values.  Synchronous. */
+int nws_set_printed(nws_ctx* c, const uint8_t* tie_up, int32_t keep_tenths, int32_t hdr_tenths);
+
+/* One lane per nw_stat record of d_stats (DEVICE, n records, 16-byte aligned): the printed identity
+ * in tenths, 0 .. 1000, into d_tenths (DEVICE uint16 [n]); 0xFFFF for a record with NW_FLAG_EMPTY.
+ * A record with aln_len outside [0, NWS_MAX_COLS] or n_ident outside [0, aln_len] is counted in
+ * *n_out_of_range (may be NULL), gets 0xFFFF, and makes the call return NW_E_INVALID with the other
+ * outputs written.  n == 0 launches nothing.  NW_E_STATE before nws_set_printed.  Synchronous. */
+int nws_printed(nws_ctx* c, const void* d_stats, int64_t n, uint16_t* d_tenths, int64_t* n_out_of_range,
+                float* kernel_ms);
+
+/* nws_flags for a row with an Expected_HDR amplicon.  One lane per read: ref = the tenths of its
+ * record in d_stats_ref (the pass against the amplicon), rep = d_tenths_rep[r] (nws_printed of the
+ * pass against the Expected_HDR amplicon; 0xFFFF: no repaired score, every test on it is false):
+ *   keep = !(flags & NW_FLAG_EMPTY) && (ref >= keep_tenths || rep >= keep_tenths)
+ *   pre  = NWQ_PRE_UNMODIFIED iff ref == 1000
+ *        | NWQ_PRE_HDR   iff ref < rep && rep >= hdr_tenths
+ *        | NWQ_PRE_MIXED iff ref < rep && rep <  hdr_tenths
+ * A read whose record is out of range as for nws_printed, or whose rep is neither <= 1000 nor
+ * 0xFFFF, is counted in *n_out_of_range, gets keep = 0 and pre = 0, and makes the call return
+ * NW_E_INVALID (the other outputs are written).  n == 0 launches nothing.  NW_E_STATE before
+ * nws_set_printed.  Synchronous. */
+int nws_flags_dual(nws_ctx* c, const void* d_stats_ref, const uint16_t* d_tenths_rep, int64_t n, uint8_t* d_pre,
+                   uint8_t* d_keep, int64_t* n_out_of_range, float* kernel_ms);
 
 #ifdef __cplusplus
 }
