@@ -80,7 +80,8 @@ NWD_NO_HIT, NWD_TIE = -1, -2
 
 # Every symbol include/crispr_summary.h declares.
 SUMMARY_EXPORTS = ("nws_create", "nws_destroy", "nws_last_error", "nws_set_identity", "nws_flags", "nws_summary",
-                   "nws_set_printed", "nws_printed", "nws_flags_dual")
+                   "nws_set_printed", "nws_printed", "nws_flags_dual", "nws_mask_pre", "nws_histograms")
+NWS_MAX_BINS = 65536            # nws_histograms' limit
 NWS_NO_TENTHS = 0xFFFF          # nws_printed's value for a record without a printed identity
 NWS_SLOTS = 16
 # The slots of nws_summary's output, in order (the enum of include/crispr_summary.h).
@@ -367,6 +368,9 @@ def load() -> ctypes.CDLL:
         "nws_set_printed": (c_int, [ctx_p, c_void_p, c_int32, c_int32]),
         "nws_printed": (c_int, [ctx_p, c_void_p, c_int64, c_void_p, POINTER(c_int64), POINTER(c_float)]),
         "nws_flags_dual": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, POINTER(c_int64),
+                                   POINTER(c_float)]),
+        "nws_mask_pre": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_void_p, POINTER(c_float)]),
+        "nws_histograms": (c_int, [ctx_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p, POINTER(c_int64),
                                    POINTER(c_float)]),
         "nwr_read_bam": (c_int, [c_char_p, c_void_p, c_int64, POINTER(c_void_p), c_char_p, c_int64]),
         "nwr_bam_free": (None, [c_void_p]),

@@ -22,6 +22,12 @@
 //   dual     one lane per read of a row with an Expected_HDR amplicon: the ref record's tenths by
 //            the same function, the HDR pass's stored tenths, then CORE:1849-1856, 536-548 and
 //            2014 as integer compares.
+//   mask     one lane per read: pre of a dropped read becomes NWQ_PRE_UNMODIFIED, so that the
+//            quantifier, which skips such a read before any total, counts kept reads only.
+//   hist     the summary's walk; the sizes n_inserted, n_deleted, n_mutated and n_inserted -
+//            n_deleted of a kept read go to the block's low bins in LDS (integer LDS atomics),
+//            the rare larger ones straight to the 64-bit counters; at the end the block adds its
+//            non-zero low bins to the counters, one 64-bit integer atomic each.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -205,9 +211,88 @@ __global__ __launch_bounds__(kBlk) void nws_summary_kernel(const SumArgs a) {
     }
 }
 
+struct MaskArgs {
+    const uint8_t* pre;
+    const uint8_t* keep;
+    int64_t n;
+    uint8_t* pre_q;             // may be pre itself: a lane reads and writes its own byte only
+};
+
+__global__ __launch_bounds__(kBlk) void nws_mask_pre_kernel(const MaskArgs a) {
+    const int64_t r = (int64_t)blockIdx.x * kBlk + threadIdx.x;
+    if (r < a.n) {
+        const uint8_t pre = a.pre[r];
+        a.pre_q[r] = a.keep[r] ? pre : (uint8_t)NWQ_PRE_UNMODIFIED;
+    }
+}
+
+// The low bins of the four histograms a block keeps in LDS: sizes 0 .. kLow - 1 of n_inserted,
+// n_deleted and n_mutated, and n_inserted - n_deleted in (-kLow, kLow).
+constexpr int kLow = 128;
+constexpr int kLowIndel = 2 * kLow - 1;
+constexpr int kLowBins = 3 * kLow + kLowIndel;
+
+struct HistArgs {
+    const int4* reads;          // [n] nwq_read: cls, n_mutated, n_inserted, n_deleted
+    const uint8_t* keep;
+    int64_t n;
+    int32_t bins;
+    unsigned long long* hist;   // [5 bins - 1]: ins, del, mut [bins] each, indel [2 bins - 1]; then bad [1].  Zeroed.
+};
+
+__global__ __launch_bounds__(kBlk) void nws_histograms_kernel(const HistArgs a) {
+    __shared__ uint32_t low[kLowBins];  // a block counts at most n / gridDim.x + kBlk < 2^32 reads
+    for (int i = threadIdx.x; i < kLowBins; i += kBlk) low[i] = 0;
+    __syncthreads();
+    const int lane = threadIdx.x & 63;
+    const int bins = a.bins;
+    unsigned long long* const g_indel = a.hist + 3 * (int64_t)bins;
+    uint32_t nbad = 0;                  // uniform in the wavefront
+    const int64_t step = (int64_t)gridDim.x * kBlk;
+    for (int64_t base = (int64_t)blockIdx.x * kBlk; base < a.n; base += step) {
+        const int64_t r = base + threadIdx.x;
+        bool counted = false;
+        int4 q = make_int4(0, 0, 0, 0);
+        if (r < a.n) {
+            q = a.reads[r];
+            counted = a.keep[r] != 0 && q.x >= 0;
+        }
+        const unsigned ub = (unsigned)bins;     // (a negative value is a large unsigned one)
+        const bool outside = counted && ((unsigned)q.y >= ub || (unsigned)q.z >= ub || (unsigned)q.w >= ub);
+        if (counted && !outside) {
+            // 0 <= v < bins: the LDS bin when v < kLow, else the global counter which * bins + v
+            auto bump = [&](int which, int v) {
+                if (v < kLow) atomicAdd(&low[which * kLow + v], 1u);
+                else atomicAdd(&a.hist[which * (int64_t)bins + v], 1ull);
+            };
+            bump(0, q.z);
+            bump(1, q.w);
+            bump(2, q.y);
+            const int d = q.z - q.w;            // -bins < d < bins
+            if (d > -kLow && d < kLow) atomicAdd(&low[3 * kLow + d + kLow - 1], 1u);
+            else atomicAdd(&g_indel[d + bins - 1], 1ull);
+        }
+        nbad += (uint32_t)__popcll(__ballot(outside));
+    }
+    __syncthreads();
+    for (int i = threadIdx.x; i < kLowBins; i += kBlk) {
+        const uint32_t v = low[i];
+        if (!v) continue;
+        if (i < 3 * kLow) {
+            const int which = i / kLow, bin = i % kLow;
+            if (bin < bins) atomicAdd(&a.hist[which * (int64_t)bins + bin], (unsigned long long)v);
+        } else {
+            const int d = i - 3 * kLow - (kLow - 1);
+            if (d > -bins && d < bins) atomicAdd(&g_indel[d + bins - 1], (unsigned long long)v);
+        }
+    }
+    if (lane == 0 && nbad) atomicAdd(a.hist + 5 * (int64_t)bins - 1, (unsigned long long)nbad);
+}
+
 }  // namespace nws
 
 struct nws_ctx : hd::DevContext {
+    hd::DevBuf<unsigned long long> d_hist;     // nws_histograms: [5 bins - 1] and the bad count
     int32_t max_cols = -1;         // -1: no tables yet
     hd::DevBuf<int32_t> d_keep_min, d_unmod_min;
     hd::DevBuf<unsigned long long> d_counters;
@@ -416,6 +501,75 @@ int nws_summary(nws_ctx* c, const void* d_reads, const uint8_t* d_pre, const uin
     if (kernel_ms) *kernel_ms = ms;
     for (int s = 1; s < NWS_SLOTS; ++s) out[s] = (int64_t)ctr[s];
     out[NWS_N] = n;
+    return NW_OK;
+}
+
+int nws_mask_pre(nws_ctx* c, const uint8_t* d_pre, const uint8_t* d_keep, int64_t n, uint8_t* d_pre_q,
+                 float* kernel_ms) {
+    if (!c) return NW_E_INVALID;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
+    if (n == 0) return NW_OK;
+    if (!d_pre || !d_keep || !d_pre_q) return fail(c, NW_E_INVALID, "null device array");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    nws::MaskArgs a{};
+    a.pre = d_pre;
+    a.keep = d_keep;
+    a.n = n;
+    a.pre_q = d_pre_q;
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(nws::nws_mask_pre_kernel, dim3((unsigned)((n + nws::kBlk - 1) / nws::kBlk)), dim3(nws::kBlk), 0, st,
+                       a);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[1], st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    if (kernel_ms) *kernel_ms = ms;
+    return NW_OK;
+}
+
+int nws_histograms(nws_ctx* c, const void* d_reads, const uint8_t* d_keep, int64_t n, int32_t bins, int64_t* out,
+                   int64_t* n_out_of_range, float* kernel_ms) {
+    if (!c) return NW_E_INVALID;
+    if (n_out_of_range) *n_out_of_range = 0;
+    if (kernel_ms) *kernel_ms = 0.0f;
+    if (bins < 1 || bins > NWS_MAX_BINS)
+        return fail(c, NW_E_UNSUPPORTED, "%d bins: 1 to %d are supported", (int)bins, NWS_MAX_BINS);
+    if (!out) return fail(c, NW_E_INVALID, "null output");
+    const size_t words = 5 * (size_t)bins - 1;
+    std::memset(out, 0, sizeof(int64_t) * words);
+    if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
+    if (n == 0) return NW_OK;
+    if (!d_reads || !d_keep) return fail(c, NW_E_INVALID, "null device array");
+    if ((uintptr_t)d_reads % 16) return fail(c, NW_E_INVALID, "the reads' results are not 16-byte aligned");
+    HIP_TRY(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, c->d_hist.reserve(words + 1));
+    HIP_TRY(c, hipMemsetAsync(c->d_hist.p, 0, sizeof(unsigned long long) * (words + 1), st));
+    nws::HistArgs a{};
+    a.reads = (const int4*)d_reads;
+    a.keep = d_keep;
+    a.n = n;
+    a.bins = bins;
+    a.hist = c->d_hist.p;
+    const int64_t blocks = std::min<int64_t>((n + nws::kBlk - 1) / nws::kBlk, nws::kMaxBlocks);
+    HIP_TRY(c, hipEventRecord(c->ev[0], st));
+    hipLaunchKernelGGL(nws::nws_histograms_kernel, dim3((unsigned)blocks), dim3(nws::kBlk), 0, st, a);
+    HIP_TRY(c, hipGetLastError());
+    HIP_TRY(c, hipEventRecord(c->ev[1], st));
+    unsigned long long bad = 0;
+    static_assert(sizeof(unsigned long long) == sizeof(int64_t), "the counters are copied as they are");
+    HIP_TRY(c, hipMemcpyAsync(out, c->d_hist.p, sizeof(int64_t) * words, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipMemcpyAsync(&bad, c->d_hist.p + words, sizeof bad, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    float ms = 0.0f;
+    HIP_TRY(c, hipEventElapsedTime(&ms, c->ev[0], c->ev[1]));
+    if (kernel_ms) *kernel_ms = ms;
+    if (n_out_of_range) *n_out_of_range = (int64_t)bad;
+    if (bad)
+        return fail(c, NW_E_INVALID, "%llu counted reads with a size outside [0, %d)", bad, (int)bins);
     return NW_OK;
 }
 

@@ -494,6 +494,7 @@ class GpuSummarizer:
         self.flags_ms = self.summary_ms = 0.0
         self.printed_key: Optional[Tuple[float, float]] = None     # (min_identity_score, threshold) of set_printed
         self.printed_ms = 0.0
+        self.mask_ms = self.histograms_ms = 0.0
 
     def close(self) -> None:
         if getattr(self, "_ctx", None):
@@ -589,6 +590,27 @@ class GpuSummarizer:
         self._check(rc, "nws_summary")
         return out
 
+    def mask_pre(self, d_pre: int, d_keep: int, n: int, d_pre_q: int) -> None:
+        """``nws_mask_pre``: ``pre`` with every dropped read's byte set to UNMODIFIED, for the
+        quantifier (uint8 [n] on the device; ``d_pre_q`` may be ``d_pre``)."""
+        ms = ctypes.c_float()
+        rc = self._lib.nws_mask_pre(self._ctx, d_pre, d_keep, n, d_pre_q, ctypes.byref(ms))
+        self.mask_ms = float(ms.value)
+        self._check(rc, "nws_mask_pre")
+
+    def histograms(self, d_reads: int, d_keep: int, n: int, bins: int):
+        """``nws_histograms``: ``(ins, del, mut, indel)`` of the kept reads of n nwq_read records
+        on the device, int64 ``[bins]`` each and ``[2 bins - 1]``.  A counted read with a size
+        outside ``[0, bins)`` raises :class:`SummaryError` with their number."""
+        bins = int(bins)
+        out = np.zeros(max(5 * bins - 1, 1), np.int64)
+        bad, ms = ctypes.c_int64(), ctypes.c_float()
+        rc = self._lib.nws_histograms(self._ctx, d_reads, d_keep, n, bins, _lib.ptr(out), ctypes.byref(bad),
+                                      ctypes.byref(ms))
+        self.histograms_ms = float(ms.value)
+        self._check(rc, "nws_histograms", int(bad.value))
+        return out[:bins], out[bins:2 * bins], out[2 * bins:3 * bins], out[3 * bins:]
+
 
 _DEFAULT_SUMMARIZER: Dict[int, GpuSummarizer] = {}
 
@@ -677,7 +699,7 @@ def check_summary_rows(rows: Sequence[dict], allow_hdr: bool = False) -> List[st
 
 
 def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, what, min_identity_score, quant_kw,
-                      on_group, hdrs=None, hdr_threshold: float = 98.0) -> Dict[str, float]:
+                      on_group, hdrs=None, hdr_threshold: float = 98.0, reports=None) -> Dict[str, float]:
     """The per-group body of :func:`summarize_pooled` and of
     :func:`crispresso_amd.regions.summarize_regions`: for every ``g`` in ``keep``, in that order,
     ``prepare(g, amplicons[g])`` (the caller's ``set_reference`` and adoption: the group's reads
@@ -690,9 +712,17 @@ def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, 
     body above runs with ``nws_flags_dual`` in place of ``nws_flags``.  The Expected_HDR pass goes
     first, so the ops the quantifier and ``on_group`` see are the amplicon pass's.
 
+    With ``reports`` (a callable ``reports(g, GroupReport)``) the quantifier runs on
+    ``nws_mask_pre`` of the flags, so that its totals hold the kept reads only as the reference's
+    do (a dropped read's ``cls`` becomes 0, which no slot counts: the slots are the same either
+    way); ``nws_summary`` still takes the flags themselves.  Then ``nws_histograms`` and the
+    :class:`crispresso_amd.report.GroupReport`, handed over after ``on_group``.  The returned
+    times gain ``mask`` and ``histograms``.  Without ``reports`` none of this runs.
+
     Errors name the group as ``"<what> <Name>"``.  The aligner's output mode and the quantifier's
     module globals are restored.  Returns the summed kernel times (``flags``, ``summary``,
     ``quantify``, ``printed``) and ``hdr_pass``, the host's wall ms of the Expected_HDR passes."""
+    import contextlib
     import time
     import types
 
@@ -704,11 +734,16 @@ def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, 
     mode = getattr(aligner, "output_mode", "rows")
     saved_globals = quantify._GLOBALS
     hdrs = hdrs or [None] * len(rows)
+    if reports is not None:
+        from .report import GroupReport
+
+        times.update(mask=0.0, histograms=0.0)
     most_hdr = max((2 * most for g in keep if hdrs[g]), default=0)
     aligner.set_output("ops")
     try:
         with DeviceBuffer(most, device) as d_pre, DeviceBuffer(most, device) as d_keep, \
-                DeviceBuffer(16 * most, device) as d_out, DeviceBuffer(most_hdr, device) as d_rep:
+                DeviceBuffer(16 * most, device) as d_out, DeviceBuffer(most_hdr, device) as d_rep, \
+                (DeviceBuffer(most, device) if reports is not None else contextlib.nullcontext()) as d_pre_q:
             for g in keep:
                 amp, row, hdr = amplicons[g], rows[g], hdrs[g]
                 try:
@@ -730,6 +765,9 @@ def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, 
                     else:
                         s.ensure_identity(min_identity_score, int(dev["max_cols"]))
                         s.flags(dev["stats"], n, d_pre.ptr, d_keep.ptr)
+                    if reports is not None:
+                        s.mask_pre(d_pre.ptr, d_keep.ptr, n, d_pre_q.ptr)
+                        times["mask"] += s.mask_ms
                 except SummaryError as exc:
                     raise SummaryError(f"{what} {row['Name']}: {exc}", exc.code, exc.n_out_of_range) from None
                 args = types.SimpleNamespace(
@@ -737,7 +775,7 @@ def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, 
                     expected_hdr_amplicon_seq=hdr, hdr_perfect_alignment_threshold=hdr_threshold, **quant_kw)
                 try:
                     q.set_params(quantify.globals_from_args(args), args, amplicon_has_n="N" in amp.upper())
-                    q.run_device_ops(amp, dev, d_pre.ptr, n, d_out.ptr)
+                    totals = q.run_device_ops(amp, dev, d_pre.ptr if reports is None else d_pre_q.ptr, n, d_out.ptr)
                 except quantify.QuantificationError as exc:     # (e.g. an amplicon too long for the quantifier's LDS)
                     raise quantify.QuantificationError(f"{what} {row['Name']}: {exc}") from None
                 times["quantify"] += q.last_kernel_ms
@@ -750,6 +788,16 @@ def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, 
                         "(LEN_AMPLICON bases)")
                 if on_group is not None:
                     on_group(g, aligner, n)
+                if reports is not None:
+                    try:
+                        hist = s.histograms(d_out.ptr, d_keep.ptr, n, int(dev["max_cols"]) + 1)
+                    except SummaryError as exc:
+                        raise SummaryError(f"{what} {row['Name']}: {exc}", exc.code, exc.n_out_of_range) from None
+                    times["histograms"] += s.histograms_ms
+                    cuts = quantify.compute_cut_points(amp, args.guide_seq, args.cleavage_offset)
+                    reports(g, GroupReport(row["Name"], amp, cuts, n, out[g].copy(),
+                                           q.unpack_totals(totals, int(dev["max_cols"])), *hist,
+                                           has_coding_seq=bool(args.coding_seq), has_expected_hdr=bool(hdr)))
     finally:
         quantify._GLOBALS = saved_globals
         aligner.set_output(mode)
@@ -763,7 +811,7 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
                      hide_mutations_outside_window_NHEJ: bool = False, k: int = 16, min_hits: int = 2,
                      both_strands: bool = True, on_group=None, demultiplexer: Optional[GpuDemultiplexer] = None,
                      quantifier=None, summarizer: Optional[GpuSummarizer] = None, allow_hdr: bool = False,
-                     hdr_perfect_alignment_threshold: float = 98.0) -> PooledSummary:
+                     hdr_perfect_alignment_threshold: float = 98.0, reports=None) -> PooledSummary:
     """Raw reads to CRISPRessoPooled's SAMPLES_QUANTIFICATION_SUMMARY.txt (amplicon mode) with the
     reads in HBM from the first kernel to the last.
 
@@ -792,11 +840,20 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
     holds the amplicons only: an HDR allele's read reaches its amplicon through the windows
     outside the edit.
 
+    With ``reports``, a callable ``reports(g, report)``, every summarized amplicon also yields a
+    :class:`crispresso_amd.report.GroupReport`: the slots, the quantifier's effect vectors,
+    counters and frameshift histograms over the kept reads (``nws_mask_pre`` hands the dropped
+    reads to the quantifier as UNMODIFIED, which it skips before any total, as the reference
+    drops them before it quantifies) and the four size histograms (``nws_histograms``, counted
+    in HBM).  :func:`crispresso_amd.report.write_report` makes the reference's
+    ``CRISPResso_on_<name>`` folder of one.  ``counts`` and ``frame`` are the same with and
+    without ``reports``.
+
     Differences from the reference, deliberate: a read is aligned in the orientation the
     demultiplexer chose and is not retried reverse-complemented; an ``Expected_HDR`` row is
-    refused unless ``allow_hdr``; the quantifier's effect vectors and histograms (not returned
-    here) are not masked by the identity filter.  A kept read that is not an alignment of its
-    amplicon (slot 15) raises :class:`crispresso_amd.quantify.QuantificationError`."""
+    refused unless ``allow_hdr``; without ``reports`` the quantifier's effect vectors and
+    histograms (not returned then) are not masked by the identity filter.  A kept read that is
+    not an alignment of its amplicon (slot 15) raises :class:`crispresso_amd.quantify.QuantificationError`."""
     from . import quantify
     from .frontend import ResidentReads
 
@@ -847,7 +904,7 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
                                    ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
                                    ignore_deletions=ignore_deletions,
                                    hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ), on_group,
-                              hdrs, float(hdr_perfect_alignment_threshold))
+                              hdrs, float(hdr_perfect_alignment_threshold), reports)
     frame = summary_frame([row["Name"] for row in rows], out, counts.tolist(), skipped)
     return PooledSummary(out, frame, res, skipped, times)
 
@@ -960,10 +1017,27 @@ def _resident_fastq(rows, fastq, fastq_r2, device, k, min_hits, both_strands, mi
             return rr.headers, seqs, quals, res, None
 
 
+def _folder_writer(out_dir: str, folders: Dict[int, str], refused: List[int]):
+    """A ``reports`` callback that writes every group's folder under ``out_dir`` and notes a group
+    without a kept read in ``refused``."""
+    from . import report
+
+    def write(g: int, rep) -> None:
+        folder = os.path.join(out_dir, report.folder_name(rep.name))
+        try:
+            report.write_report(folder, rep)
+        except report.ReportError:
+            refused.append(g)
+        else:
+            folders[g] = folder
+
+    return write
+
+
 def demultiplex_fastq(amplicons_file: str, fastq: str, out_dir: str, *, k: int = 16, min_hits: int = 2,
                       both_strands: bool = True, min_reads_to_use_region: int = 1000, device: int = 0,
                       fastq_r2: Optional[str] = None, front: Optional[dict] = None,
-                      summary: Optional[dict] = None) -> dict:
+                      summary: Optional[dict] = None, reports: bool = False) -> dict:
     """The command line's work; returns what it wrote.
 
     With ``fastq_r2``, ``front`` (keyword arguments of ``frontend.prepare_fastq_resident``: the
@@ -971,11 +1045,20 @@ def demultiplex_fastq(amplicons_file: str, fastq: str, out_dir: str, *, k: int =
     :func:`summarize_pooled`, ``{}`` for its defaults) the files go through the GPU front end:
     the per-amplicon FASTQ files then hold the merged (filtered, trimmed) reads under R1's
     headers with FLASH's ``/1`` cut, and with ``summary`` SAMPLES_QUANTIFICATION_SUMMARY.txt is
-    written as well."""
+    written as well.  With ``reports`` (needs ``summary``) every summarized amplicon with a kept
+    read gets its ``CRISPResso_on_<name>`` folder (:func:`crispresso_amd.report.write_report`)
+    under ``out_dir``: ``report_folders`` maps its index to the folder, ``reports_refused`` lists
+    the indices without a kept read."""
     from . import ingest
 
     rows = read_amplicons_file(amplicons_file)
     ps = None
+    folders: Dict[int, str] = {}
+    refused: List[int] = []
+    if reports:
+        if summary is None:
+            raise ValueError("reports are written from the summary: pass summary as well")
+        summary = dict(summary, reports=_folder_writer(out_dir, folders, refused))
     if fastq_r2 is not None or front or summary is not None:
         names, seqs, quals, res, ps = _resident_fastq(rows, fastq, fastq_r2, device, k, min_hits, both_strands,
                                                       min_reads_to_use_region, front or {}, summary)
@@ -1008,6 +1091,8 @@ def demultiplex_fastq(amplicons_file: str, fastq: str, out_dir: str, *, k: int =
         out["summary"] = ps
         out["summary_file"] = os.path.join(out_dir, "SAMPLES_QUANTIFICATION_SUMMARY.txt")
         write_summary(out["summary_file"], ps.frame)
+    if reports:
+        out["report_folders"], out["reports_refused"] = folders, refused
     return out
 
 
@@ -1038,6 +1123,9 @@ def build_parser():
     g = p.add_argument_group("the per-amplicon summary")
     g.add_argument("--summary", action="store_true",
                    help="align and quantify every amplicon's reads and write SAMPLES_QUANTIFICATION_SUMMARY.txt")
+    g.add_argument("--reports", action="store_true",
+                   help="with --summary: write a CRISPResso_on_<name> folder per summarized amplicon (editing "
+                        "frequencies, effect vectors, size histograms), as CRISPRessoCompare reads them")
     g.add_argument("--min_identity_score", type=float, default=60.0)
     g.add_argument("--window_around_sgrna", type=int, default=1)
     g.add_argument("--cleavage_offset", type=int, default=-3)
@@ -1091,6 +1179,10 @@ def options_from_args(p, args) -> dict:
             98.0 if args.hdr_perfect_alignment_threshold is None else args.hdr_perfect_alignment_threshold)
     elif args.hdr_perfect_alignment_threshold is not None:
         p.error("--hdr_perfect_alignment_threshold is used only with --hdr")
+    if args.reports:
+        if not args.summary:
+            p.error("--reports is used only with --summary")
+        kw["reports"] = True
     return kw
 
 
@@ -1114,6 +1206,10 @@ def main(argv=None) -> int:
           f"{args.min_reads_to_use_region:g} reads: {out['report']}")
     if "summary_file" in out:
         print(f"summary of {len(out['rows']) - len(out['summary'].skipped)} amplicons: {out['summary_file']}")
+    if "report_folders" in out:
+        print(f"{len(out['report_folders'])} result folders under {args.output_folder}")
+        for g in out["reports_refused"]:
+            print(f"amplicon {out['rows'][g]['Name']}: no read passed the identity filter, no folder is written")
     return 0
 
 

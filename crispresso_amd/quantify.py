@@ -373,6 +373,38 @@ def quantify_alignments(df_needle_alignment: pd.DataFrame, args, quantifier: Opt
 
 # ------------------------------------------------------------------ run summary
 
+def size_tables(indel, n_inserted, n_deleted, n_mutated, len_amplicon: int, cut_points: Sequence[int]) -> Dict:
+    """The histogram half of :func:`run_summary` from four integer columns (pandas Series or
+    arrays; ``indel`` is ``n_inserted - n_deleted`` = ``effective_len - LEN_AMPLICON`` per read,
+    the others one value per read, and each column may come in any order): ``df_indels``,
+    ``df_insertion``, ``df_deletion``, ``df_substitution`` as described there.  ``np.histogram`` closes its last bin on the right,
+    so a table's last row also counts the value one past it; the range of a size table is
+    ``max(15, round(p99 of the non-zero values))`` with numpy's linear interpolation and
+    round-half-even, 15 without a non-zero value."""
+    L = int(len_amplicon)
+    out: Dict = {}
+    if len(cut_points):
+        xmin, xmax = -min(cut_points), L - max(cut_points)
+    else:
+        xmin, xmax = -(L // 2), L // 2
+    hdensity, hlengths = np.histogram(np.asarray(indel, dtype=np.int64), np.arange(xmin, xmax))
+    out["df_indels"] = pd.DataFrame(np.vstack([hlengths[:-1], hdensity]).T, columns=["indel_size", "fq"])
+
+    def calculate_range(col):
+        nz = col[col > 0]
+        try:
+            return max(15, int(np.round(np.percentile(nz, 99))))
+        except Exception:   # empty selection, as the reference's bare except (CORE:2349)
+            return 15
+
+    for name, col, size_col, sign in (("df_insertion", n_inserted, "ins_size", 1),
+                                      ("df_deletion", n_deleted, "del_size", -1),
+                                      ("df_substitution", n_mutated, "sub_size", 1)):
+        y, x = np.histogram(col, bins=range(0, calculate_range(col)))
+        out[name] = pd.DataFrame(np.vstack([sign * x[:-1], y]).T, columns=[size_col, "fq"])
+    return out
+
+
 def run_summary(df: pd.DataFrame, len_amplicon: int, cut_points: Sequence[int]) -> Dict:
     """The per-run aggregates ``run_crispresso`` returns after the quantification
     (the values tests/crispresso_tests.py:181-195 asserts), from the quantified
@@ -400,25 +432,7 @@ def run_summary(df: pd.DataFrame, len_amplicon: int, cut_points: Sequence[int]) 
         for what, col in (("inserted", "n_inserted"), ("deleted", "n_deleted"), ("mutated", "n_mutated")):
             out[f"{tag}_{what}"] = int(np.sum(sel[col] > 0))
     eff = L + df["n_inserted"].to_numpy(dtype=np.int64) - df["n_deleted"].to_numpy(dtype=np.int64)
-    if len(cut_points):
-        xmin, xmax = -min(cut_points), L - max(cut_points)
-    else:
-        xmin, xmax = -(L // 2), L // 2
-    hdensity, hlengths = np.histogram(eff - L, np.arange(xmin, xmax))
-    out["df_indels"] = pd.DataFrame(np.vstack([hlengths[:-1], hdensity]).T, columns=["indel_size", "fq"])
-
-    def calculate_range(col):
-        nz = df.loc[df[col] > 0, col]
-        try:
-            return max(15, int(np.round(np.percentile(nz, 99))))
-        except Exception:   # empty selection, as the reference's bare except (CORE:2349)
-            return 15
-
-    for name, col, size_col, sign in (("df_insertion", "n_inserted", "ins_size", 1),
-                                      ("df_deletion", "n_deleted", "del_size", -1),
-                                      ("df_substitution", "n_mutated", "sub_size", 1)):
-        y, x = np.histogram(df[col], bins=range(0, calculate_range(col)))
-        out[name] = pd.DataFrame(np.vstack([sign * x[:-1], y]).T, columns=[size_col, "fq"])
+    out.update(size_tables(eff - L, df["n_inserted"], df["n_deleted"], df["n_mutated"], L, cut_points))
     alleles = df.groupby(["align_seq", "ref_seq", "NHEJ", "UNMODIFIED", "HDR", "n_deleted", "n_inserted",
                           "n_mutated"]).size().reset_index()
     alleles = alleles.rename(columns={0: "#Reads", "align_seq": "Aligned_Sequence", "ref_seq": "Reference_Sequence"})

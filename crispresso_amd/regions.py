@@ -705,7 +705,7 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
                       ignore_substitutions: bool = False, ignore_insertions: bool = False,
                       ignore_deletions: bool = False, hide_mutations_outside_window_NHEJ: bool = False, on_group=None,
                       quantifier=None, summarizer=None, allow_hdr: bool = False,
-                      hdr_perfect_alignment_threshold: float = 98.0) -> RegionSummary:
+                      hdr_perfect_alignment_threshold: float = 98.0, reports=None) -> RegionSummary:
     """A BAM's region reads to SAMPLES_QUANTIFICATION_SUMMARY.txt (CRISPRessoWGS, and
     CRISPRessoPooled's genome mode) with the reads in HBM from the BAM's 4-bit codes to the 16
     counters: what :func:`crispresso_amd.demux.summarize_pooled` is for amplicon mode.
@@ -731,6 +731,11 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
     the region is adopted and aligned twice, ``nws_printed`` keeps the printed identity to the
     Expected_HDR amplicon and ``nws_flags_dual`` applies the reference's rule on the two printed
     identities with ``hdr_perfect_alignment_threshold``, as ``summarize_pooled`` explains.
+
+    With ``reports``, a callable ``reports(g, report)``, every analysed region also yields a
+    :class:`crispresso_amd.report.GroupReport` (the quantifier's totals over the kept reads and
+    the size histograms, both made in HBM), as ``summarize_pooled`` explains; ``counts`` and
+    ``frame`` are the same with and without it.
 
     Deliberate differences: an ``Expected_HDR`` row is refused unless ``allow_hdr``, as in
     ``summarize_pooled``; discovered regions carry no ``Expected_HDR``; there
@@ -785,7 +790,7 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
              exclude_bp_from_left=exclude_bp_from_left, exclude_bp_from_right=exclude_bp_from_right,
              ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
              ignore_deletions=ignore_deletions, hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ),
-        on_group, hdrs if allow_hdr else None, float(hdr_perfect_alignment_threshold))
+        on_group, hdrs if allow_hdr else None, float(hdr_perfect_alignment_threshold), reports)
     frame = demux.summary_frame([row["Name"] for row in rows], out, n_reads, skipped)
     return RegionSummary(out, frame, skipped, times, n_reads)
 
@@ -928,7 +933,8 @@ def region_sequences(fasta_path: str, regions: Sequence[Region]) -> List[str]:
 
 def _summary_main(args, bam: BamRecords, hdr_options: dict) -> int:
     """``--summary``: SAMPLES_QUANTIFICATION_SUMMARY.txt of the regions of a file (CRISPRessoWGS;
-    --min-reads defaults to its 10) or of the discovered ones (genome mode: --min-reads as given)."""
+    --min-reads defaults to its 10) or of the discovered ones (genome mode: --min-reads as given).
+    With ``--reports`` also a ``CRISPResso_on_<name>`` folder per analysed region with a kept read."""
     import os
 
     from . import demux
@@ -944,11 +950,16 @@ def _summary_main(args, bam: BamRecords, hdr_options: dict) -> int:
                                        args.eqx_as_match, args.device)
         min_reads = args.min_reads or 10
     os.makedirs(args.out, exist_ok=True)
+    folders: dict = {}
+    refused: list = []
+    writer = demux._folder_writer(args.out, folders, refused) if args.reports else None
     with res, GpuAligner(args.device) as aligner:
-        summary = summarize_regions(rows, res, aligner, min_reads=min_reads, **hdr_options)
+        summary = summarize_regions(rows, res, aligner, min_reads=min_reads, reports=writer, **hdr_options)
     demux.write_summary(os.path.join(args.out, "SAMPLES_QUANTIFICATION_SUMMARY.txt"), summary.frame)
     for row, n in zip(rows, summary.n_reads):
         print(f"{row['Name']}\t{n}")
+    for g in refused:
+        print(f"region {rows[g]['Name']}: no read passed the identity filter, no folder is written")
     return 0
 
 
@@ -970,6 +981,9 @@ def build_parser():
     p.add_argument("--summary", action="store_true",
                    help="with --regions or --discover, and --genome: align and quantify every region in HBM and write "
                         "SAMPLES_QUANTIFICATION_SUMMARY.txt; no FASTQ is written, the bases never reach the host")
+    p.add_argument("--reports", action="store_true",
+                   help="with --summary: write a CRISPResso_on_<name> folder per analysed region (editing frequencies, "
+                        "effect vectors, size histograms), as CRISPRessoCompare reads them")
     p.add_argument("--reference-order", action="store_true",
                    help="with --discover: reads in the order the reference's sort leaves them (C locale)")
     p.add_argument("--out", required=True, help="output directory")
@@ -1003,6 +1017,8 @@ def main(argv=None) -> int:
     p = build_parser()
     args = p.parse_args(argv)
     hdr_options = summary_options(p, args)
+    if args.reports and not args.summary:
+        p.error("--reports is used only with --summary")
     if args.summary and not args.genome:
         p.error("--summary needs --genome, the regions' amplicons come from it")
     if args.summary and (args.by_reference or args.reference_order):

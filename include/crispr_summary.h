@@ -120,6 +120,36 @@ int nws_printed(nws_ctx* c, const void* d_stats, int64_t n, uint16_t* d_tenths, 
 int nws_flags_dual(nws_ctx* c, const void* d_stats_ref, const uint16_t* d_tenths_rep, int64_t n, uint8_t* d_pre,
                    uint8_t* d_keep, int64_t* n_out_of_range, float* kernel_ms);
 
+/* ---- per-group reports: the identity filter on the quantifier's input, the size histograms ------
+ *
+ * The reference drops the reads below min_identity_score before it quantifies (CORE:1869, 2025), so
+ * its effect vectors, frameshift counters and histograms hold kept reads only.  It also skips a row
+ * that is UNMODIFIED before it touches any of them (CORE:480-481), and so does every path of the
+ * quantifier for a read whose pre has NWQ_PRE_UNMODIFIED.  A dropped read handed to the quantifier
+ * as UNMODIFIED therefore adds nothing to the totals: masking pre is masking the read.
+ *
+ * nws_mask_pre: one lane per read, d_pre_q[r] = d_keep[r] ? d_pre[r] : NWQ_PRE_UNMODIFIED (the HDR
+ * and MIXED bits of a dropped read are cleared).  d_pre, d_keep, d_pre_q DEVICE uint8 [n]; d_pre_q
+ * may be d_pre itself.  n == 0 launches nothing.  kernel_ms may be NULL.  Synchronous. */
+int nws_mask_pre(nws_ctx* c, const uint8_t* d_pre, const uint8_t* d_keep, int64_t n, uint8_t* d_pre_q,
+                 float* kernel_ms);
+
+#define NWS_MAX_BINS 65536
+
+/* The size histograms of a report (CORE:2345-2365, 2903-2905) from d_reads (DEVICE nwq_read [n],
+ * 16-byte aligned) and d_keep (DEVICE uint8 [n]) into out (HOST int64 [5 * bins - 1]):
+ *   ins [bins], del [bins], mut [bins]: the counts of n_inserted, n_deleted, n_mutated;
+ *   indel [2 * bins - 1]: entry d + bins - 1 counts d = n_inserted - n_deleted.
+ * Only reads with keep != 0 and cls >= 0 are counted.  A counted read with any of the three values
+ * outside [0, bins) is counted in *n_out_of_range (may be NULL) and in no histogram, and makes the
+ * call return NW_E_INVALID (the other reads' counts are written all the same).  1 <= bins <=
+ * NWS_MAX_BINS, else NW_E_UNSUPPORTED; the caller passes max(len_amplicon, longest read) + 1.
+ * Integer sums (LDS atomics per block for the low bins, one 64-bit atomic per non-zero bin per
+ * block): the result is a function of the input alone.  n == 0 returns zeros and launches nothing.
+ * kernel_ms may be NULL.  Synchronous. */
+int nws_histograms(nws_ctx* c, const void* d_reads, const uint8_t* d_keep, int64_t n, int32_t bins, int64_t* out,
+                   int64_t* n_out_of_range, float* kernel_ms);
+
 #ifdef __cplusplus
 }
 #endif
