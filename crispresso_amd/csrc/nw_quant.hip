@@ -945,6 +945,9 @@ struct nwq_ctx {
     uint32_t flags = 0;
     int32_t window = 0;
     int64_t lane_fallbacks = -1;     // the last nwq_run_device_ops' quant_lanes fallback count
+    // what the last run launched with (nwq_last_plan): row kernel waves a block, totals in HBM, grid,
+    // LDS bytes; quant_lanes' waves a block, LDS bytes; expand_rows' waves a block; row kernel over a list
+    int32_t plan[8] = {};
     std::vector<int32_t> prefix;     // host copy of QArgs::prefix
     hd::DevBuf<int32_t> d_prefix;
     hd::DevBuf<uint32_t> d_partial;
@@ -1050,6 +1053,11 @@ int run_impl(nwq_ctx* c, uint8_t* d_aln, int64_t stride, const int32_t* d_len, i
     int rc = geometry(c, stride, n, &g);
     if (rc) return rc;
     if (list) g.grid = std::min(g.grid, c->num_cus);   // a short list (usually empty): a small grid
+    c->plan[0] = g.wpb;
+    c->plan[1] = g.gtot;
+    c->plan[2] = g.grid;
+    c->plan[3] = g.lds;
+    c->plan[7] = list != nullptr;
     HIP_TRY(c, c->d_partial.reserve((size_t)(slabs0 + g.grid) * g.nwords));
     HIP_TRY(c, c->d_totals.reserve((size_t)g.nwords));
     nwq::QArgs a;
@@ -1109,6 +1117,12 @@ int run_impl(nwq_ctx* c, uint8_t* d_aln, int64_t stride, const int32_t* d_len, i
 extern "C" {
 
 int64_t nwq_lane_fallbacks(const nwq_ctx* c) { return c ? c->lane_fallbacks : -1; }
+
+int nwq_last_plan(const nwq_ctx* c, int32_t out[8]) {
+    if (!c || !out) return NW_E_INVALID;
+    std::memcpy(out, c->plan, sizeof(c->plan));
+    return NW_OK;
+}
 
 int nwq_create(int device, nwq_ctx** out) {
     if (!out) return NW_E_INVALID;
@@ -1185,6 +1199,7 @@ int nwq_run(nwq_ctx* c, uint8_t* aln, int64_t stride, const int32_t* aln_len, co
     if (n > 0 && (!aln || !aln_len || !pre || !out)) return fail(c, NW_E_INVALID, "null buffer");
     if (!totals) return fail(c, NW_E_INVALID, "null totals");
     HIP_TRY(c, hipSetDevice(c->device));
+    std::memset(c->plan, 0, sizeof(c->plan));
     const size_t nn = (size_t)std::max<int64_t>(n, 1);
     HIP_TRY(c, c->d_aln.reserve(nn * 3 * (size_t)stride));
     HIP_TRY(c, c->d_len.reserve(nn));
@@ -1213,6 +1228,7 @@ int nwq_run_device(nwq_ctx* c, uint8_t* d_aln, int64_t stride, const int32_t* d_
     if (!totals) return fail(c, NW_E_INVALID, "null totals");
     if (len_stride <= 0) return fail(c, NW_E_INVALID, "len_stride must be positive");
     HIP_TRY(c, hipSetDevice(c->device));
+    std::memset(c->plan, 0, sizeof(c->plan));
     return run_impl(c, d_aln, stride, d_aln_len, len_stride, d_pre, n, d_out, totals, kernel_ms);
 }
 
@@ -1230,6 +1246,7 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
     if (stride <= 0 || (stride & 3) || stride >= 32768)
         return fail(c, NW_E_INVALID, "stride %lld must be a positive multiple of 4 below 32768", (long long)stride);
     HIP_TRY(c, hipSetDevice(c->device));
+    std::memset(c->plan, 0, sizeof(c->plan));
     const std::string key(amplicon, amplicon + amplicon_len);
     if (key != c->amp_key) {   // the amplicon's tables (the markup's ':' test), once per amplicon
         std::vector<uint32_t> rowpos((size_t)amplicon_len);
@@ -1308,6 +1325,8 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
         la.flags = c->flags;
         hipLaunchKernelGGL(nwq::quant_lanes, dim3(grid), dim3(64 * lane_wpb), lane_lds, c->stream, la);
         HIP_TRY(c, hipGetLastError());
+        c->plan[4] = lane_wpb;
+        c->plan[5] = lane_lds;
         // the fallback reads: their rows, then the row kernel over the list
         int wpb = 4;
         while (wpb > 1 && (int64_t)wpb * 3 * stride > 64 * 1024) wpb >>= 1;
@@ -1317,6 +1336,7 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
                            (const int32_t*)d_stats, d_reads, d_offsets, reads_bias, c->d_amp.p, c->d_rowpos.p,
                            c->d_lut.p, amplicon_len, d_pre, 0, n, c->d_aln.p, stride, c->d_fb.p, c->d_fb.p + nn);
         HIP_TRY(c, hipGetLastError());
+        c->plan[6] = wpb;
         int32_t nfb = -1;
         const int rc = run_impl(c, c->d_aln.p, stride, (const int32_t*)d_stats, 8, d_pre, n, d_out, totals, kernel_ms,
                                 true, c->d_fb.p, c->d_fb.p + nn, grid, &nfb);
@@ -1334,6 +1354,7 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
                            c->d_lut.p, amplicon_len, d_pre, (int)((c->flags & nwq::F_NFIX) != 0), n, c->d_aln.p,
                            stride, nullptr, nullptr);
         HIP_TRY(c, hipGetLastError());
+        c->plan[6] = wpb;
     }
     // the records' aln_len, 8 ints apart (nw_stat)
     return run_impl(c, c->d_aln.p, stride, (const int32_t*)d_stats, 8, d_pre, n, d_out, totals, kernel_ms, true);

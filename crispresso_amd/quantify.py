@@ -236,6 +236,21 @@ class GpuQuantifier:
         self.last_lane_fallbacks = int(self._lib.nwq_lane_fallbacks(self._ctx))
         return totals
 
+    PLAN_FIELDS = ("row_waves", "row_totals_hbm", "row_grid", "row_lds", "lane_waves", "lane_lds", "expand_waves",
+                   "row_list")
+
+    def last_plan(self) -> Dict:
+        """The launch shapes of the last run / run_device / run_device_ops (nwq_last_plan):
+        the row kernel's waves a block, whether its totals were in HBM, its grid and LDS bytes,
+        quant_lanes' waves a block (0 = not used) and LDS bytes, expand_rows' waves a block
+        (0 = not run), whether the row kernel ran over quant_lanes' fallback list."""
+        out = (ctypes.c_int32 * 8)()
+        self._check(self._lib.nwq_last_plan(self._ctx, out), "nwq_last_plan")
+        d = dict(zip(self.PLAN_FIELDS, (int(v) for v in out)))
+        d["row_totals_hbm"] = bool(d["row_totals_hbm"])
+        d["row_list"] = bool(d["row_list"])
+        return d
+
     def unpack_totals(self, totals: np.ndarray, stride: int) -> Dict:
         L = self._len
         nv = _lib.NWQ_NVEC * L

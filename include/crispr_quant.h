@@ -101,6 +101,14 @@ int nwq_run_device_ops(nwq_ctx* c, const char* amplicon, int32_t amplicon_len, c
  * holds); -1 when that run did not take the lane path.  A diagnostic (bench.py reports it). */
 int64_t nwq_lane_fallbacks(const nwq_ctx* c);
 
+/* The launch shapes of the last nwq_run / nwq_run_device / nwq_run_device_ops, as launched:
+ *   out[0] the row kernel's waves a block       out[1] 1 when its totals were in HBM (quant_kernel_long)
+ *   out[2] its grid                             out[3] its LDS bytes
+ *   out[4] quant_lanes' waves a block (0 = not used)      out[5] quant_lanes' LDS bytes
+ *   out[6] expand_rows' waves a block (0 = not run)       out[7] 1 when the row kernel ran over a list
+ * All zero before the first run and after a run refused before its launch.  A diagnostic. */
+int nwq_last_plan(const nwq_ctx* c, int32_t out[8]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -218,9 +218,9 @@ def quant_args(row, hdr):
         hdr_perfect_alignment_threshold=THRESHOLD, **OPTS)
 
 
-def host_frames(batch, batch_hdr):
+def host_frames(batch, batch_hdr, score_min=SCORE):
     """(the DataFrame the reference would quantify, the same without its filter): the rows on the
-    host, both printed identities, kept iff either is > SCORE (CORE:1849-1856)."""
+    host, both printed identities, kept iff either is > score_min (CORE:1849-1856)."""
     recs, kept = [], []
     for i in range(len(batch)):
         if batch.empty(i):
@@ -229,7 +229,7 @@ def host_frames(batch, batch_hdr):
         sp = float("nan") if batch_hdr is None else \
             printed_percent(int(batch_hdr.stats["n_ident"][i]), int(batch_hdr.stats["aln_len"][i]))
         recs.append((batch.ref_seq(i), batch.align_str(i), batch.align_seq(i), sr, sp, sr - sp))
-        kept.append(sr > SCORE or sp > SCORE)
+        kept.append(sr > score_min or sp > score_min)
     df = pd.DataFrame(recs, columns=["ref_seq", "align_str", "align_seq", "score_ref", "score_repaired", "score_diff"])
     return df[np.array(kept, bool)].reset_index(drop=True), df
 
@@ -261,10 +261,10 @@ def same_totals(totals, ref):
     return None
 
 
-def check_report(rep, row, n_reads, batch, batch_hdr, slots, gq):
+def check_report(rep, row, n_reads, batch, batch_hdr, slots, gq, score_min=SCORE):
     """One GroupReport against the host path on the kept rows; returns (kept, all) oracle totals."""
     hdr = row.get("Expected_HDR") if batch_hdr is not None else None
-    kept, everything = host_frames(batch, batch_hdr)
+    kept, everything = host_frames(batch, batch_hdr, score_min)
     ref = oracle_totals(kept, row, hdr)
     assert same_totals(rep.totals, ref) is None, (row["Name"], same_totals(rep.totals, ref))
     args = quant_args(row, hdr)

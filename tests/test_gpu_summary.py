@@ -262,22 +262,22 @@ def quant_args(row):
         hide_mutations_outside_window_NHEJ=False, expected_hdr_amplicon_seq=None, **OPTS)
 
 
-def kept_frame(batch):
-    """The DataFrame the reference would quantify: the rows whose printed identity is > SCORE."""
+def kept_frame(batch, score_min=SCORE):
+    """The DataFrame the reference would quantify: the rows whose printed identity is > score_min."""
     recs = []
     for i in range(len(batch)):
         if batch.empty(i):
             continue
         score = printed_percent(int(batch.stats["n_ident"][i]), int(batch.stats["aln_len"][i]))
-        if score > SCORE:
+        if score > score_min:
             recs.append((batch.ref_seq(i), batch.align_str(i), batch.align_seq(i), score))
     return pd.DataFrame(recs, columns=["ref_seq", "align_str", "align_seq", "score_ref"])
 
 
-def host_slots(batch, row, gq):
+def host_slots(batch, row, gq, score_min=SCORE):
     """The 16 slots by the path summarize_pooled replaces: rows on the host, the printed
     identity, the filter, quantify_alignments, run_summary."""
-    df = kept_frame(batch)
+    df = kept_frame(batch, score_min)
     args = quant_args(row)
     g = quantify.globals_from_args(args)
     out = quantify.quantify_alignments(df, args, quantifier=gq, globals_=g)
@@ -285,11 +285,11 @@ def host_slots(batch, row, gq):
     return psm.slots_of_summary(quantify.run_summary(out[0], len(row["Amplicon_Sequence"]), cuts), len(batch))
 
 
-def oracle_slots(row, group_reads):
+def oracle_slots(row, group_reads, score_min=SCORE):
     """The same from the CPU oracles alone: needle, the filter, quant_oracle, the model."""
     amp = row["Amplicon_Sequence"]
     buf, off = pack(group_reads)
-    df = kept_frame(oracle_batch(amp, buf, off))
+    df = kept_frame(oracle_batch(amp, buf, off), score_min)
     cuts = qo.cut_points(amp, row["sgRNA"] or None, OPTS["cleavage_offset"])
     exon, spl = qo.exon_splicing_positions(amp, row["Coding_sequence"] or None)
     prm = qo.QuantParams(len(amp), qo.include_idxs(len(amp), cuts, OPTS["window_around_sgrna"],
