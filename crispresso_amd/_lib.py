@@ -61,7 +61,8 @@ QUANT_EXPORTS = (
 ALLELE_EXPORTS = (
     "nwa_create", "nwa_destroy", "nwa_last_error", "nwa_group_device", "nwa_last_collided", "nwa_phase_times",
     "nwa_reads_per_step", "nwa_group_host", "nwa_reads_have_lower", "nwa_windows_device", "nwa_windows_fetch",
-    "nwa_windows_collided", "nwa_windows_times",
+    "nwa_windows_collided", "nwa_windows_times", "nwa_windows_resident", "nwa_table_device", "nwa_table_fetch",
+    "nwa_table_collided", "nwa_table_times",
 )
 
 # Every symbol include/crispr_count.h declares.
@@ -337,6 +338,14 @@ def load() -> ctypes.CDLL:
         "nwa_windows_fetch": (c_int, [ctx_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
         "nwa_windows_collided": (c_int64, [ctx_p]),
         "nwa_windows_times": (c_int, [ctx_p, c_void_p]),
+        "nwa_windows_resident": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64,
+                                         c_int32, c_char_p, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p,
+                                         c_void_p, c_int32, c_void_p, POINTER(c_int64), POINTER(c_int64)]),
+        "nwa_table_device": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int32,
+                                     c_char_p, c_int32, c_void_p, c_void_p, POINTER(c_int64), POINTER(c_int32)]),
+        "nwa_table_fetch": (c_int, [ctx_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+        "nwa_table_collided": (c_int64, [ctx_p]),
+        "nwa_table_times": (c_int, [ctx_p, c_void_p]),
         "nwc_create": (c_int, [c_int, POINTER(c_void_p)]),
         "nwc_destroy": (None, [ctx_p]),
         "nwc_last_error": (c_char_p, [ctx_p]),

@@ -23,6 +23,14 @@ HBM (crispresso_amd/csrc/nw_windows.hip) and strings are built for the window gr
 * :func:`around_cut_tables`       -- one frame per cut point: from the resident batch when the
   device path takes the arguments, else ``allele_table`` + ``around_cut_from_alleles``
 * :func:`merge_around_cut_tables` -- around-cut tables of several batches -> one
+
+A resident summary (``summarize_pooled`` / ``summarize_regions``) has no text on the host and its
+keep flags and ``nwq_read`` records stay in HBM; there the rows of one read per group are built
+on the device too (crispresso_amd/csrc/nw_allele_rows.hip).  These tables are upper case.
+
+* :func:`resident_allele_table`      -- device groups + device rows -> ``df_alleles``
+* :func:`resident_around_cut_tables` -- the windows with device keep flags and results, or
+  :func:`around_cut_from_alleles` on the resident allele table
 """
 from __future__ import annotations
 
@@ -67,6 +75,22 @@ class WindowGroups:
     unedited: np.ndarray                   # uint8 [groups]: a read of the group is UNMODIFIED
     group_of_read: Optional[np.ndarray]    # int32 [n] (-1: not kept), when asked for
     collided: int = 0                      # records of the call the device pass left to the host
+
+    def __len__(self) -> int:
+        return len(self.first)
+
+
+@dataclass
+class AlleleRows:
+    """One representative per group of identical kept reads of a resident batch, in order of
+    first appearance (nwa_table_device)."""
+
+    rows: np.ndarray                       # uint8 [groups][2][row_stride]: aligned-read row, reference row, zero-padded
+    cols: np.ndarray                       # int32 [groups]: min(aln_len, awidth) of the group's first read
+    first: np.ndarray                      # int64 [groups]
+    count: np.ndarray                      # int64 [groups]
+    results: np.ndarray                    # int32 [groups][4]: the first read's nwq_read
+    collided: int = 0                      # reads the device pass left to the host
 
     def __len__(self) -> int:
         return len(self.first)
@@ -183,18 +207,33 @@ class GpuAlleleGrouper:
         n = int(n)
         keep, tag = _host_arrays(n, keep, tag)
         rr = _results_array(read_results, n)
+        return self._windows("nwa_windows_device", dev, n, awidth, amplicon, cut_points, offset, _lib.ptr(keep), tag,
+                             _lib.ptr(rr), want_group_of_read)
+
+    def windows_resident(self, dev: dict, n: int, awidth: int, amplicon: str, cut_points: Sequence[int], offset: int,
+                         d_keep: int, d_results: int, tag=None, want_group_of_read: bool = False) -> List[WindowGroups]:
+        """:meth:`windows` with the keep flags and the ``nwq_read`` records in HBM
+        (nwa_windows_resident): ``d_keep`` (uint8 ``[n]``, non-zero = kept, or 0 for all) and
+        ``d_results`` are device pointers, as a resident summary leaves them."""
+        n = int(n)
+        _, tag = _host_arrays(n, None, tag)
+        return self._windows("nwa_windows_resident", dev, n, awidth, amplicon, cut_points, offset, int(d_keep or 0), tag,
+                             int(d_results or 0), want_group_of_read)
+
+    def _windows(self, entry: str, dev: dict, n: int, awidth: int, amplicon: str, cut_points, offset: int, keep: int,
+                 tag, results: int, want_group_of_read: bool) -> List[WindowGroups]:
         cuts = np.ascontiguousarray(cut_points, dtype=np.int32)
         ng = np.zeros(max(len(cuts), 1), np.int64)
         bad, first_bad = ctypes.c_int64(), ctypes.c_int64()
         amp = amplicon.encode("ascii")
-        rc = self._lib.nwa_windows_device(self._ctx, dev["ops"], dev["ops_off"], dev["stats"], dev["reads"],
-                                          dev["offsets"], int(dev["reads_bias"]), n, int(awidth), amp, len(amp),
-                                          _lib.ptr(cuts), len(cuts), int(offset), _lib.ptr(keep), _lib.ptr(tag),
-                                          _lib.ptr(rr), int(want_group_of_read), _lib.ptr(ng), ctypes.byref(bad),
-                                          ctypes.byref(first_bad))
+        rc = getattr(self._lib, entry)(self._ctx, dev["ops"], dev["ops_off"], dev["stats"], dev["reads"],
+                                       dev["offsets"], int(dev["reads_bias"]), n, int(awidth), amp, len(amp),
+                                       _lib.ptr(cuts), len(cuts), int(offset), keep, _lib.ptr(tag),
+                                       results, int(want_group_of_read), _lib.ptr(ng), ctypes.byref(bad),
+                                       ctypes.byref(first_bad))
         if rc != 0:
             msg = self._lib.nwa_last_error(self._ctx).decode(errors="replace")
-            raise AlleleError(f"nwa_windows_device failed ({rc}): {msg}")
+            raise AlleleError(f"{entry} failed ({rc}): {msg}")
         if bad.value:
             raise AlleleError(f"{bad.value} kept reads have no column for the cut point in their first "
                               f"min(aln_len, awidth) columns; the first is read {first_bad.value}")
@@ -211,6 +250,38 @@ class GpuAlleleGrouper:
                 raise AlleleError(f"nwa_windows_fetch({k}) failed ({rc})")
             out.append(w)
         return out
+
+    def table_times(self) -> Dict[str, float]:
+        """Device ms of the last :meth:`table` by phase."""
+        ms = np.zeros(2, np.float32)
+        self._lib.nwa_table_times(self._ctx, _lib.ptr(ms))
+        return dict(zip(("group", "rows"), (float(x) for x in ms)))
+
+    def table(self, dev: dict, n: int, awidth: int, amplicon: str, d_keep: int, d_results: int) -> AlleleRows:
+        """The representative rows of a device-resident batch whose keep flags and ``nwq_read``
+        records are in HBM as well (nwa_table_device): ``dev`` is ``GpuAligner.device_ops()``,
+        ``d_keep`` (uint8 ``[n]``, non-zero = kept, or 0 for all) and ``d_results`` are device
+        pointers.  The kept reads are grouped by their bytes and one wavefront per group builds
+        the two rows of its first read in HBM; only the groups' rows come back.  The bytes are
+        upper case, as the whole resident path is.  Raises :class:`AlleleError` when a
+        representative's runs do not match its bytes or the amplicon."""
+        n = int(n)
+        amp = amplicon.encode("ascii")
+        ng, stride = ctypes.c_int64(), ctypes.c_int32()
+        rc = self._lib.nwa_table_device(self._ctx, dev["ops"], dev["ops_off"], dev["stats"], dev["reads"], dev["offsets"],
+                                        int(dev["reads_bias"]), n, int(awidth), amp, len(amp), int(d_keep or 0),
+                                        int(d_results or 0), ctypes.byref(ng), ctypes.byref(stride))
+        if rc != 0:
+            msg = self._lib.nwa_last_error(self._ctx).decode(errors="replace")
+            raise AlleleError(f"nwa_table_device failed ({rc}): {msg}")
+        g, w = int(ng.value), max(int(stride.value), 16)
+        t = AlleleRows(np.zeros((g, 2, w), np.uint8), np.zeros(g, np.int32), np.zeros(g, np.int64), np.zeros(g, np.int64),
+                       np.zeros((g, 4), np.int32), int(self._lib.nwa_table_collided(self._ctx)))
+        rc = self._lib.nwa_table_fetch(self._ctx, _lib.ptr(t.rows), _lib.ptr(t.cols), _lib.ptr(t.first), _lib.ptr(t.count),
+                                       _lib.ptr(t.results))
+        if rc != 0:
+            raise AlleleError(f"nwa_table_fetch failed ({rc})")
+        return t
 
 
 _DEFAULT: Dict[int, GpuAlleleGrouper] = {}
@@ -481,4 +552,70 @@ def around_cut_tables(aligner, amplicon: str, buf: np.ndarray, offsets: np.ndarr
         ops_batch = aligner.download_ops(n)
     groups = group_reads_host(buf, offsets, keep, tag) if dev is not None else group_reads(aligner, buf, offsets, keep, tag)
     table = allele_table(amplicon, buf, offsets, ops_batch, rr, groups, nthreads)
+    return [around_cut_from_alleles(table, c, offset) for c in cuts]
+
+
+# ------------------------------------------------------------------ from a resident summary: no text on the host
+
+def resident_allele_table(dev: dict, n: int, awidth: int, amplicon: str, d_keep: int, d_results: int,
+                          device: int = 0, grouper: Optional[GpuAlleleGrouper] = None) -> pd.DataFrame:
+    """:func:`allele_table` of a resident batch whose reads, keep flags and ``nwq_read`` records
+    never left HBM (a group of :func:`crispresso_amd.demux.summarize_pooled` or
+    :func:`crispresso_amd.regions.summarize_regions` after its quantifier pass): ``dev`` is
+    ``GpuAligner.device_ops()``, ``d_keep`` / ``d_results`` are device pointers.
+
+    :meth:`GpuAlleleGrouper.table` groups the kept reads by their bytes and builds the two rows of
+    one read per group in HBM; the strings are made of those rows here, NHEJ / UNMODIFIED / HDR
+    come from ``cls`` as :func:`allele_table` maps them, and the reference's own last steps
+    finish the frame.  Byte-identical reads against one amplicon (or amplicon + Expected_HDR pair)
+    have identical runs, flags and ``nwq_read``, and the resident paths never retry a read
+    reverse-complemented, so the byte groups are the reference's groups.  The resident bytes are
+    upper case, as the whole resident path is: a lower-case input base shows upper case here."""
+    t = (grouper or default_grouper(device)).table(dev, n, awidth, amplicon, d_keep, d_results)
+    if not len(t):
+        return merge_allele_tables([])
+    res = t.results
+    cls = res[:, 0]
+    if (cls < 0).any():
+        raise AlleleError(f"reads are not aligned to the amplicon (LEN_AMPLICON bases): {t.first[cls < 0][:5].tolist()}")
+    stride = t.rows.shape[2]
+    cols = t.cols.tolist()
+    seq_rows = t.rows[:, 0, :].tobytes()
+    ref_rows = t.rows[:, 1, :].tobytes()
+    frame = pd.DataFrame({
+        "Aligned_Sequence": [seq_rows[q * stride:q * stride + c].decode("ascii") for q, c in enumerate(cols)],
+        "Reference_Sequence": [ref_rows[q * stride:q * stride + c].decode("ascii") for q, c in enumerate(cols)],
+        "NHEJ": cls == 1, "UNMODIFIED": cls == 0, "HDR": cls == 2,
+        "n_deleted": res[:, 3].astype(np.int64), "n_inserted": res[:, 2].astype(np.int64),
+        "n_mutated": res[:, 1].astype(np.int64),
+        "#Reads": t.count.astype(np.int64),
+    }, columns=KEYS + ["#Reads"])
+    return _finish(frame)
+
+
+def resident_around_cut_tables(dev: dict, n: int, awidth: int, amplicon: str, cut_points: Sequence[int], offset: int,
+                               d_keep: int, d_results: int, table: Optional[pd.DataFrame] = None, device: int = 0,
+                               grouper: Optional[GpuAlleleGrouper] = None) -> List[pd.DataFrame]:
+    """:func:`around_cut_tables` of a resident batch whose keep flags and ``nwq_read`` records
+    are in HBM: one frame per cut point in the form of :func:`around_cut_from_alleles`.  Through
+    nwa_windows_resident when :func:`windows_on_device` holds; otherwise
+    :func:`around_cut_from_alleles` on ``table``, the batch's :func:`resident_allele_table`
+    (made here when not given).  Neither way needs a read's text.  Upper case, as
+    :func:`resident_allele_table` explains."""
+    cuts = [int(c) for c in cut_points]
+    if not cuts:
+        return []
+    if windows_on_device(amplicon, cuts, offset):
+        out = []
+        g = grouper or default_grouper(device)
+        for w in g.windows_resident(dev, n, awidth, amplicon, cuts, offset, d_keep, d_results):
+            lens = w.win_len.tolist()
+            width = w.win.shape[2]
+            a_rows, r_rows = w.win[:, 0, :].tobytes(), w.win[:, 1, :].tobytes()
+            out.append(_finish_around([a_rows[q * width:q * width + c].decode("ascii") for q, c in enumerate(lens)],
+                                      [r_rows[q * width:q * width + c].decode("ascii") for q, c in enumerate(lens)],
+                                      w.unedited, w.count))
+        return out
+    if table is None:
+        table = resident_allele_table(dev, n, awidth, amplicon, d_keep, d_results, device, grouper)
     return [around_cut_from_alleles(table, c, offset) for c in cuts]

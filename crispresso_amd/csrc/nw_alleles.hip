@@ -227,6 +227,16 @@ __global__ __launch_bounds__(256) void coll_info_kernel(Args a, const uint32_t* 
     out[i] = c;
 }
 
+// The non-zero bytes of keep[n]: a sum per block, one atomic per block (an integer sum: the same
+// total in any order; n < 2^31).
+__global__ __launch_bounds__(256) void count_kept_kernel(const uint8_t* keep, int64_t n, uint32_t* total) {
+    uint32_t v = 0;
+    for (int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x; r < n; r += (int64_t)gridDim.x * 256) v += keep[r] != 0;
+    uint32_t sum;
+    block_scan<4>(v, &sum);
+    if (threadIdx.x == 0 && sum) atomicAdd(total, sum);
+}
+
 }  // namespace nwa
 
 namespace {
@@ -270,49 +280,33 @@ uint64_t host_hash(const unsigned char* p, int64_t n, int32_t tag) {
 
 }  // namespace
 
-extern "C" {
+namespace nwa {
 
-int nwa_create(int device, nwa_ctx** out) {
-    const int rc = hd::create_context(device, nwa::kEvents, out);
-    if (rc != NW_OK) return rc;
-    nwa_ctx* c = *out;
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->num_cus = prop.multiProcessorCount;
-    c->hash_bits = grp::env_hash_bits("CRISPR_NWA_HASH_BITS");
+int count_kept(nwa_ctx* c, const uint8_t* d_keep, int64_t n, int64_t* kept) {
+    *kept = n;
+    if (!d_keep || n <= 0) return NW_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    HIP_TRY(c, c->d_counters.reserve(4));
+    hipStream_t st = c->stream;
+    HIP_TRY(c, hipMemsetAsync(c->d_counters.p, 0, sizeof(uint32_t) * 4, st));
+    const unsigned grid = (unsigned)std::min<int64_t>((n + 255) / 256, (int64_t)16 * c->num_cus);
+    hipLaunchKernelGGL(count_kept_kernel, dim3(grid), dim3(256), 0, st, d_keep, n, c->d_counters.p + 3);
+    HIP_TRY(c, hipGetLastError());
+    uint32_t total = 0;
+    HIP_TRY(c, hipMemcpyAsync(&total, c->d_counters.p + 3, sizeof total, hipMemcpyDeviceToHost, st));
+    HIP_TRY(c, hipStreamSynchronize(st));
+    if ((int64_t)total > n) return fail(c, NW_E_STATE, "inconsistent kept count");
+    *kept = total;
     return NW_OK;
 }
 
-void nwa_destroy(nwa_ctx* c) { hd::destroy_context(c); }
-
-const char* nwa_last_error(const nwa_ctx* c) { return c ? c->err.c_str() : "null context"; }
-
-int64_t nwa_last_collided(const nwa_ctx* c) { return c ? c->collided : -1; }
-
-int nwa_phase_times(const nwa_ctx* c, float* ms) {
-    if (!c || !ms) return NW_E_INVALID;
-    std::memcpy(ms, c->phase_ms, sizeof c->phase_ms);
-    return NW_OK;
-}
-
-int64_t nwa_reads_per_step(const nwa_ctx* c) { return c ? (int64_t)4 * 16 * c->num_cus : -1; }
-
-int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offsets, int64_t reads_bias, int64_t n,
-                     const uint8_t* keep, const int32_t* tag, int64_t* first, int64_t* count, int64_t cap,
-                     int32_t* group_of_read, int64_t* n_groups, float* kernel_ms) {
-    if (!c) return NW_E_INVALID;
-    if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
-    if (!n_groups || cap < 0 || (cap > 0 && (!first || !count)))
-        return fail(c, NW_E_INVALID, "null output array");
-    if (n > 0 && (!d_reads || !d_offsets)) return fail(c, NW_E_INVALID, "null device array");
+int group_resident(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offsets, int64_t reads_bias, int64_t n,
+                   const uint8_t* d_keep, int64_t kept, const int32_t* tag, int64_t* first, int64_t* count,
+                   int64_t cap, int32_t* group_of_read, int64_t* n_groups, float* kernel_ms) {
     c->collided = 0;
     std::fill(c->phase_ms, c->phase_ms + 4, 0.0f);
     if (kernel_ms) *kernel_ms = 0.0f;
     *n_groups = 0;
-    int64_t kept = n;
-    if (keep) {
-        kept = 0;
-        for (int64_t r = 0; r < n; ++r) kept += keep[r] != 0;
-    }
     if (kept == 0) {
         if (group_of_read) std::fill(group_of_read, group_of_read + n, -1);
         return NW_OK;
@@ -336,10 +330,6 @@ int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offset
     HIP_TRY(c, c->d_gfirst.reserve((size_t)kept));
     HIP_TRY(c, c->d_gcount.reserve((size_t)kept));
     HIP_TRY(c, c->d_gor.reserve((size_t)n));
-    if (keep) {
-        HIP_TRY(c, c->d_keep.reserve((size_t)n));
-        HIP_TRY(c, hipMemcpy(c->d_keep.p, keep, (size_t)n, hipMemcpyHostToDevice));
-    }
     if (tag) {
         HIP_TRY(c, c->d_tag.reserve((size_t)n));
         HIP_TRY(c, hipMemcpy(c->d_tag.p, tag, sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice));
@@ -349,7 +339,7 @@ int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offset
     a.off = d_offsets;
     a.bias = reads_bias;
     a.n = n;
-    a.keep = keep ? c->d_keep.p : nullptr;
+    a.keep = d_keep;
     a.tag = tag ? c->d_tag.p : nullptr;
     a.hash = c->d_hash.p;
     a.slot = c->d_slot.p;
@@ -473,6 +463,56 @@ int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offset
         for (int64_t k = 0; k < nc; ++k) group_of_read[coll[(size_t)k]] = (int32_t)new_id[(size_t)cgrp[(size_t)k]];
     }
     return NW_OK;
+}
+
+}  // namespace nwa
+
+extern "C" {
+
+int nwa_create(int device, nwa_ctx** out) {
+    const int rc = hd::create_context(device, nwa::kEvents, out);
+    if (rc != NW_OK) return rc;
+    nwa_ctx* c = *out;
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device) == hipSuccess) c->num_cus = prop.multiProcessorCount;
+    c->hash_bits = grp::env_hash_bits("CRISPR_NWA_HASH_BITS");
+    return NW_OK;
+}
+
+void nwa_destroy(nwa_ctx* c) { hd::destroy_context(c); }
+
+const char* nwa_last_error(const nwa_ctx* c) { return c ? c->err.c_str() : "null context"; }
+
+int64_t nwa_last_collided(const nwa_ctx* c) { return c ? c->collided : -1; }
+
+int nwa_phase_times(const nwa_ctx* c, float* ms) {
+    if (!c || !ms) return NW_E_INVALID;
+    std::memcpy(ms, c->phase_ms, sizeof c->phase_ms);
+    return NW_OK;
+}
+
+int64_t nwa_reads_per_step(const nwa_ctx* c) { return c ? (int64_t)4 * 16 * c->num_cus : -1; }
+
+int nwa_group_device(nwa_ctx* c, const uint8_t* d_reads, const int64_t* d_offsets, int64_t reads_bias, int64_t n,
+                     const uint8_t* keep, const int32_t* tag, int64_t* first, int64_t* count, int64_t cap,
+                     int32_t* group_of_read, int64_t* n_groups, float* kernel_ms) {
+    if (!c) return NW_E_INVALID;
+    if (n < 0 || n > 0x7FFFFFFFll) return fail(c, NW_E_INVALID, "read count %lld out of range", (long long)n);
+    if (!n_groups || cap < 0 || (cap > 0 && (!first || !count)))
+        return fail(c, NW_E_INVALID, "null output array");
+    if (n > 0 && (!d_reads || !d_offsets)) return fail(c, NW_E_INVALID, "null device array");
+    int64_t kept = n;
+    if (keep) {
+        kept = 0;
+        for (int64_t r = 0; r < n; ++r) kept += keep[r] != 0;
+    }
+    if (keep && kept > 0) {
+        HIP_TRY(c, hipSetDevice(c->device));
+        HIP_TRY(c, c->d_keep.reserve((size_t)n));
+        HIP_TRY(c, hipMemcpy(c->d_keep.p, keep, (size_t)n, hipMemcpyHostToDevice));
+    }
+    return nwa::group_resident(c, d_reads, d_offsets, reads_bias, n, keep ? c->d_keep.p : nullptr, kept, tag, first, count,
+                               cap, group_of_read, n_groups, kernel_ms);
 }
 
 int nwa_group_host(const char* reads, const int64_t* offsets, int64_t n, const uint8_t* keep, const int32_t* tag,

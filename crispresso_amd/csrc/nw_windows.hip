@@ -12,10 +12,13 @@
 //            block then copies its 128 records, contiguous in the [cuts][n][stride] record
 //            buffer, with coalesced dword stores.  The amplicon is staged in LDS once per block.
 //   group    the records of one cut point are n "reads" of `stride` bytes at r * stride:
-//            nwa_group_device (nw_alleles.hip: hash / insert / verify / compaction, the
-//            collided records grouped exactly on the host) groups them as it stands.
+//            nwa::group_resident (nw_alleles.hip, the body of nwa_group_device: hash / insert /
+//            verify / compaction, the collided records grouped exactly on the host) groups them
+//            as it stands, on the keep flags where they lie on the device.
 //   finish   unedited[g] = OR over the group's reads of cls == 0 (every writer stores the same
 //            1), and the records of the groups' first reads gathered for the copy back.
+// nwa_windows_device takes keep and the nwq_read records as HOST arrays, nwa_windows_resident as
+// DEVICE arrays (a resident summary's d_keep / d_out): one body.
 #include <cstring>
 
 #include "nwa_device.h"
@@ -153,17 +156,26 @@ __global__ __launch_bounds__(256) void window_gather_kernel(const uint32_t* rec,
     out[i] = rec[(int64_t)first[g] * s4 + (i - g * s4)];
 }
 
+// unmod[r] = the nwq_read of read r has cls == 0
+__global__ __launch_bounds__(256) void window_unmod_kernel(const int32_t* results, int64_t n, uint8_t* unmod) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r < n) unmod[r] = results[4 * r] == 0;
+}
+
 }  // namespace nwa
 
 using hd::fail;
 
-extern "C" {
+namespace {
 
-int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_off, const void* d_stats,
-                       const uint8_t* d_reads, const int64_t* d_offsets, int64_t reads_bias, int64_t n, int32_t awidth,
-                       const char* amplicon, int32_t amp_len, const int32_t* cut_points, int32_t n_cuts, int32_t offset,
-                       const uint8_t* keep, const int32_t* tag, const int32_t* read_results, int32_t want_group_of_read,
-                       int64_t* n_groups, int64_t* n_no_cut, int64_t* first_no_cut) {
+// The body of nwa_windows_device and nwa_windows_resident.  on_device: keep and read_results are
+// DEVICE arrays (the kept count comes from a device reduction, cls == 0 is tested there);
+// otherwise HOST arrays, copied to the device here.
+int windows_body(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_off, const void* d_stats, const uint8_t* d_reads,
+                 const int64_t* d_offsets, int64_t reads_bias, int64_t n, int32_t awidth, const char* amplicon,
+                 int32_t amp_len, const int32_t* cut_points, int32_t n_cuts, int32_t offset, const uint8_t* keep,
+                 const int32_t* tag, const int32_t* read_results, bool on_device, int32_t want_group_of_read,
+                 int64_t* n_groups, int64_t* n_no_cut, int64_t* first_no_cut) {
     if (!c) return NW_E_INVALID;
     c->w_tab.clear();
     c->w_cuts = 0;
@@ -193,7 +205,10 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
     c->w_tab.resize((size_t)n_cuts);
     for (int32_t k = 0; k < n_cuts; ++k) n_groups[k] = 0;
     int64_t kept = n;
-    if (keep) {
+    if (keep && on_device) {
+        const int rc = nwa::count_kept(c, keep, n, &kept);
+        if (rc != NW_OK) return rc;
+    } else if (keep) {
         kept = 0;
         for (int64_t r = 0; r < n; ++r) kept += keep[r] != 0;
     }
@@ -212,15 +227,23 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
     HIP_TRY(c, c->w_err.reserve(2));
     HIP_TRY(c, c->w_gfirst.reserve((size_t)kept));
     HIP_TRY(c, c->w_gun.reserve((size_t)kept));
-    if (keep) {
-        HIP_TRY(c, c->d_keep.reserve((size_t)n));
-        HIP_TRY(c, hipMemcpy(c->d_keep.p, keep, (size_t)n, hipMemcpyHostToDevice));
-    }
-    std::vector<uint8_t> unmod((size_t)n);
-    for (int64_t r = 0; r < n; ++r) unmod[(size_t)r] = read_results[4 * r] == 0;
-    HIP_TRY(c, hipMemcpy(c->w_unmod.p, unmod.data(), (size_t)n, hipMemcpyHostToDevice));
-    HIP_TRY(c, hipMemcpy(c->w_amp.p, amplicon, (size_t)amp_len, hipMemcpyHostToDevice));
     hipStream_t st = c->stream;
+    const uint8_t* d_keep = keep;
+    if (on_device) {
+        hipLaunchKernelGGL(nwa::window_unmod_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, read_results, n,
+                           c->w_unmod.p);
+        HIP_TRY(c, hipGetLastError());
+    } else {
+        if (keep) {
+            HIP_TRY(c, c->d_keep.reserve((size_t)n));
+            HIP_TRY(c, hipMemcpy(c->d_keep.p, keep, (size_t)n, hipMemcpyHostToDevice));
+            d_keep = c->d_keep.p;
+        }
+        std::vector<uint8_t> unmod((size_t)n);
+        for (int64_t r = 0; r < n; ++r) unmod[(size_t)r] = read_results[4 * r] == 0;
+        HIP_TRY(c, hipMemcpy(c->w_unmod.p, unmod.data(), (size_t)n, hipMemcpyHostToDevice));
+    }
+    HIP_TRY(c, hipMemcpy(c->w_amp.p, amplicon, (size_t)amp_len, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(nwa::window_offsets_kernel, dim3((unsigned)(n / 256 + 1)), dim3(256), 0, st, c->w_off.p, n,
                        (int64_t)stride);
     HIP_TRY(c, hipGetLastError());
@@ -241,7 +264,7 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
         a.awidth = awidth;
         a.amp = c->w_amp.p;
         a.La = amp_len;
-        a.keep = keep ? c->d_keep.p : nullptr;
+        a.keep = d_keep;
         a.K = K;
         for (int k = 0; k < nwa::kWinCuts; ++k) a.cut[k] = k < K ? cut_points[k0 + k] : 0;
         a.offset = offset;
@@ -275,8 +298,8 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
             nwa::WinTable& t = c->w_tab[(size_t)(k0 + k)];
             const uint8_t* rec_k = c->w_rec.p + (size_t)k * (size_t)n * (size_t)stride;
             int64_t ng = 0;
-            const int rc = nwa_group_device(c, rec_k, c->w_off.p, 0, n, keep, tag, first.data(), count.data(), kept,
-                                            gor.data(), &ng, &ms);
+            const int rc = nwa::group_resident(c, rec_k, c->w_off.p, 0, n, d_keep, kept, tag, first.data(), count.data(),
+                                               kept, gor.data(), &ng, &ms);
             if (rc != NW_OK) return rc;
             if (ng <= 0 || ng > kept) return fail(c, NW_E_STATE, "inconsistent window group count");
             c->w_ms[1] += ms;
@@ -319,6 +342,30 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
         }
     }
     return NW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_off, const void* d_stats,
+                       const uint8_t* d_reads, const int64_t* d_offsets, int64_t reads_bias, int64_t n, int32_t awidth,
+                       const char* amplicon, int32_t amp_len, const int32_t* cut_points, int32_t n_cuts, int32_t offset,
+                       const uint8_t* keep, const int32_t* tag, const int32_t* read_results, int32_t want_group_of_read,
+                       int64_t* n_groups, int64_t* n_no_cut, int64_t* first_no_cut) {
+    return windows_body(c, d_ops, d_ops_off, d_stats, d_reads, d_offsets, reads_bias, n, awidth, amplicon, amp_len,
+                        cut_points, n_cuts, offset, keep, tag, read_results, false, want_group_of_read, n_groups, n_no_cut,
+                        first_no_cut);
+}
+
+int nwa_windows_resident(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_off, const void* d_stats,
+                         const uint8_t* d_reads, const int64_t* d_offsets, int64_t reads_bias, int64_t n, int32_t awidth,
+                         const char* amplicon, int32_t amp_len, const int32_t* cut_points, int32_t n_cuts, int32_t offset,
+                         const uint8_t* d_keep, const int32_t* tag, const int32_t* d_results, int32_t want_group_of_read,
+                         int64_t* n_groups, int64_t* n_no_cut, int64_t* first_no_cut) {
+    return windows_body(c, d_ops, d_ops_off, d_stats, d_reads, d_offsets, reads_bias, n, awidth, amplicon, amp_len,
+                        cut_points, n_cuts, offset, d_keep, tag, d_results, true, want_group_of_read, n_groups, n_no_cut,
+                        first_no_cut);
 }
 
 int nwa_windows_fetch(const nwa_ctx* c, int32_t k, uint8_t* win, int32_t* win_len, int64_t* first, int64_t* count,

@@ -699,7 +699,8 @@ def check_summary_rows(rows: Sequence[dict], allow_hdr: bool = False) -> List[st
 
 
 def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, what, min_identity_score, quant_kw,
-                      on_group, hdrs=None, hdr_threshold: float = 98.0, reports=None) -> Dict[str, float]:
+                      on_group, hdrs=None, hdr_threshold: float = 98.0, reports=None, alleles: bool = False,
+                      offset_around_cut: int = 20) -> Dict[str, float]:
     """The per-group body of :func:`summarize_pooled` and of
     :func:`crispresso_amd.regions.summarize_regions`: for every ``g`` in ``keep``, in that order,
     ``prepare(g, amplicons[g])`` (the caller's ``set_reference`` and adoption: the group's reads
@@ -719,6 +720,16 @@ def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, 
     :class:`crispresso_amd.report.GroupReport`, handed over after ``on_group``.  The returned
     times gain ``mask`` and ``histograms``.  Without ``reports`` none of this runs.
 
+    With ``alleles`` (needs ``reports``: :class:`ValueError` without) the report also gets the
+    group's allele table and its tables around the cut sites (``offset_around_cut`` columns each
+    side), made after ``nws_histograms`` from the resident ops, the keep flags and the
+    ``nwq_read`` records where they lie (:func:`crispresso_amd.alleles.resident_allele_table`,
+    :func:`crispresso_amd.alleles.resident_around_cut_tables`): no read's text reaches the host.
+    The tables are upper case.  The returned times gain ``alleles`` and ``around_cut`` (the
+    kernels' ms of ``nwa_table_device`` and ``nwa_windows_resident``; 0 for tables that took the
+    host fallback) and ``alleles_wall`` / ``around_cut_wall`` (the host's wall ms, strings and
+    frames included).  Without ``alleles`` no kernel more runs and no buffer more is allocated.
+
     Errors name the group as ``"<what> <Name>"``.  The aligner's output mode and the quantifier's
     module globals are restored.  Returns the summed kernel times (``flags``, ``summary``,
     ``quantify``, ``printed``) and ``hdr_pass``, the host's wall ms of the Expected_HDR passes."""
@@ -734,10 +745,18 @@ def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, 
     mode = getattr(aligner, "output_mode", "rows")
     saved_globals = quantify._GLOBALS
     hdrs = hdrs or [None] * len(rows)
+    if alleles and reports is None:
+        raise ValueError("alleles=True fills the groups' reports: pass reports as well")
     if reports is not None:
-        from .report import GroupReport
+        from .report import GroupReport, guide_cut_pairs
 
         times.update(mask=0.0, histograms=0.0)
+    if alleles:
+        from . import alleles as al_tables
+
+        times.update(alleles=0.0, around_cut=0.0, alleles_wall=0.0, around_cut_wall=0.0)
+        awidth = int(aligner.options.awidth)
+        grouper = al_tables.default_grouper(device)
     most_hdr = max((2 * most for g in keep if hdrs[g]), default=0)
     aligner.set_output("ops")
     try:
@@ -795,9 +814,30 @@ def _summarize_groups(rows, amplicons, keep, most, prepare, aligner, q, s, out, 
                         raise SummaryError(f"{what} {row['Name']}: {exc}", exc.code, exc.n_out_of_range) from None
                     times["histograms"] += s.histograms_ms
                     cuts = quantify.compute_cut_points(amp, args.guide_seq, args.cleavage_offset)
+                    table = around = None
+                    if alleles:
+                        try:
+                            t0 = time.perf_counter()
+                            table = al_tables.resident_allele_table(dev, n, awidth, amp, d_keep.ptr, d_out.ptr, device,
+                                                                    grouper)
+                            t1 = time.perf_counter()
+                            times["alleles"] += sum(grouper.table_times().values())
+                            pairs = guide_cut_pairs(args.guide_seq, cuts)
+                            pair_cuts = [c for _, c in pairs]
+                            frames = al_tables.resident_around_cut_tables(
+                                dev, n, awidth, amp, pair_cuts, int(offset_around_cut), d_keep.ptr, d_out.ptr, table,
+                                device, grouper)
+                            around = [(sg, c, f) for (sg, c), f in zip(pairs, frames)]
+                            if pairs and al_tables.windows_on_device(amp, pair_cuts, int(offset_around_cut)):
+                                times["around_cut"] += sum(grouper.window_times().values())
+                            times["alleles_wall"] += (t1 - t0) * 1e3
+                            times["around_cut_wall"] += (time.perf_counter() - t1) * 1e3
+                        except al_tables.AlleleError as exc:
+                            raise al_tables.AlleleError(f"{what} {row['Name']}: {exc}") from None
                     reports(g, GroupReport(row["Name"], amp, cuts, n, out[g].copy(),
                                            q.unpack_totals(totals, int(dev["max_cols"])), *hist,
-                                           has_coding_seq=bool(args.coding_seq), has_expected_hdr=bool(hdr)))
+                                           has_coding_seq=bool(args.coding_seq), has_expected_hdr=bool(hdr),
+                                           alleles=table, around_cut=around))
     finally:
         quantify._GLOBALS = saved_globals
         aligner.set_output(mode)
@@ -811,7 +851,8 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
                      hide_mutations_outside_window_NHEJ: bool = False, k: int = 16, min_hits: int = 2,
                      both_strands: bool = True, on_group=None, demultiplexer: Optional[GpuDemultiplexer] = None,
                      quantifier=None, summarizer: Optional[GpuSummarizer] = None, allow_hdr: bool = False,
-                     hdr_perfect_alignment_threshold: float = 98.0, reports=None) -> PooledSummary:
+                     hdr_perfect_alignment_threshold: float = 98.0, reports=None, alleles: bool = False,
+                     offset_around_cut: int = 20) -> PooledSummary:
     """Raw reads to CRISPRessoPooled's SAMPLES_QUANTIFICATION_SUMMARY.txt (amplicon mode) with the
     reads in HBM from the first kernel to the last.
 
@@ -849,6 +890,15 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
     ``CRISPResso_on_<name>`` folder of one.  ``counts`` and ``frame`` are the same with and
     without ``reports``.
 
+    With ``alleles`` (needs ``reports``) every report also carries the amplicon's allele table
+    (``report.alleles``, the reference's ``df_alleles``) and its tables around the cut sites
+    (``report.around_cut``, ``offset_around_cut`` columns each side, the reference's
+    ``--offset_around_cut_to_plot``): identical kept reads are grouped in HBM and the rows of one
+    read per group are built there (``nwa_table_device``, ``nwa_windows_resident``), so the
+    group's text never exists on the host.  These tables are upper case, as the whole resident
+    path is.  :func:`crispresso_amd.report.write_report` then writes
+    ``Alleles_frequency_table.txt`` and the around-cut files as well.
+
     Differences from the reference, deliberate: a read is aligned in the orientation the
     demultiplexer chose and is not retried reverse-complemented; an ``Expected_HDR`` row is
     refused unless ``allow_hdr``; without ``reports`` the quantifier's effect vectors and
@@ -858,6 +908,8 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
     from .frontend import ResidentReads
 
     k, min_hits = check_params(k, min_hits)
+    if alleles and reports is None:
+        raise ValueError("alleles=True fills the amplicons' reports: pass reports as well")
     amplicons = check_summary_rows(rows, allow_hdr)
     hdrs = [checked_expected_hdr(row, amp) for row, amp in zip(rows, amplicons)] if allow_hdr else None
     abuf, aoff = pack_amplicons(amplicons)
@@ -904,7 +956,8 @@ def summarize_pooled(rows: Sequence[dict], reads, aligner, *, min_reads: int = 1
                                    ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
                                    ignore_deletions=ignore_deletions,
                                    hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ), on_group,
-                              hdrs, float(hdr_perfect_alignment_threshold), reports)
+                              hdrs, float(hdr_perfect_alignment_threshold), reports, bool(alleles),
+                              int(offset_around_cut))
     frame = summary_frame([row["Name"] for row in rows], out, counts.tolist(), skipped)
     return PooledSummary(out, frame, res, skipped, times)
 
@@ -1037,7 +1090,8 @@ def _folder_writer(out_dir: str, folders: Dict[int, str], refused: List[int]):
 def demultiplex_fastq(amplicons_file: str, fastq: str, out_dir: str, *, k: int = 16, min_hits: int = 2,
                       both_strands: bool = True, min_reads_to_use_region: int = 1000, device: int = 0,
                       fastq_r2: Optional[str] = None, front: Optional[dict] = None,
-                      summary: Optional[dict] = None, reports: bool = False) -> dict:
+                      summary: Optional[dict] = None, reports: bool = False, alleles: bool = False,
+                      offset_around_cut: int = 20) -> dict:
     """The command line's work; returns what it wrote.
 
     With ``fastq_r2``, ``front`` (keyword arguments of ``frontend.prepare_fastq_resident``: the
@@ -1048,17 +1102,23 @@ def demultiplex_fastq(amplicons_file: str, fastq: str, out_dir: str, *, k: int =
     written as well.  With ``reports`` (needs ``summary``) every summarized amplicon with a kept
     read gets its ``CRISPResso_on_<name>`` folder (:func:`crispresso_amd.report.write_report`)
     under ``out_dir``: ``report_folders`` maps its index to the folder, ``reports_refused`` lists
-    the indices without a kept read."""
+    the indices without a kept read.  With ``alleles`` (needs ``reports``) the folders also get
+    ``Alleles_frequency_table.txt`` and the tables around the cut sites, ``offset_around_cut``
+    columns each side (:func:`summarize_pooled`'s ``alleles``)."""
     from . import ingest
 
     rows = read_amplicons_file(amplicons_file)
     ps = None
+    if alleles and not reports:
+        raise ValueError("the allele tables go into the result folders: pass reports as well")
     folders: Dict[int, str] = {}
     refused: List[int] = []
     if reports:
         if summary is None:
             raise ValueError("reports are written from the summary: pass summary as well")
         summary = dict(summary, reports=_folder_writer(out_dir, folders, refused))
+        if alleles:
+            summary.update(alleles=True, offset_around_cut=int(offset_around_cut))
     if fastq_r2 is not None or front or summary is not None:
         names, seqs, quals, res, ps = _resident_fastq(rows, fastq, fastq_r2, device, k, min_hits, both_strands,
                                                       min_reads_to_use_region, front or {}, summary)
@@ -1126,6 +1186,11 @@ def build_parser():
     g.add_argument("--reports", action="store_true",
                    help="with --summary: write a CRISPResso_on_<name> folder per summarized amplicon (editing "
                         "frequencies, effect vectors, size histograms), as CRISPRessoCompare reads them")
+    g.add_argument("--alleles", action="store_true",
+                   help="with --reports: also write Alleles_frequency_table.txt and, per sgRNA, "
+                        "Alleles_frequency_table_around_cut_site_for_<sgRNA>.txt into every folder (upper case)")
+    g.add_argument("--offset_around_cut_to_plot", type=int, default=None,
+                   help="with --alleles: the columns each side of the cut site in the around-cut tables (default 20)")
     g.add_argument("--min_identity_score", type=float, default=60.0)
     g.add_argument("--window_around_sgrna", type=int, default=1)
     g.add_argument("--cleavage_offset", type=int, default=-3)
@@ -1183,6 +1248,13 @@ def options_from_args(p, args) -> dict:
         if not args.summary:
             p.error("--reports is used only with --summary")
         kw["reports"] = True
+    if args.alleles:
+        if not args.reports:
+            p.error("--alleles is used only with --reports")
+        kw["alleles"] = True
+        kw["offset_around_cut"] = 20 if args.offset_around_cut_to_plot is None else args.offset_around_cut_to_plot
+    elif args.offset_around_cut_to_plot is not None:
+        p.error("--offset_around_cut_to_plot is used only with --alleles")
     return kw
 
 

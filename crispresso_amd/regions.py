@@ -705,7 +705,8 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
                       ignore_substitutions: bool = False, ignore_insertions: bool = False,
                       ignore_deletions: bool = False, hide_mutations_outside_window_NHEJ: bool = False, on_group=None,
                       quantifier=None, summarizer=None, allow_hdr: bool = False,
-                      hdr_perfect_alignment_threshold: float = 98.0, reports=None) -> RegionSummary:
+                      hdr_perfect_alignment_threshold: float = 98.0, reports=None, alleles: bool = False,
+                      offset_around_cut: int = 20) -> RegionSummary:
     """A BAM's region reads to SAMPLES_QUANTIFICATION_SUMMARY.txt (CRISPRessoWGS, and
     CRISPRessoPooled's genome mode) with the reads in HBM from the BAM's 4-bit codes to the 16
     counters: what :func:`crispresso_amd.demux.summarize_pooled` is for amplicon mode.
@@ -735,7 +736,10 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
     With ``reports``, a callable ``reports(g, report)``, every analysed region also yields a
     :class:`crispresso_amd.report.GroupReport` (the quantifier's totals over the kept reads and
     the size histograms, both made in HBM), as ``summarize_pooled`` explains; ``counts`` and
-    ``frame`` are the same with and without it.
+    ``frame`` are the same with and without it.  With ``alleles`` (needs ``reports``) every
+    report also carries the region's allele table and its tables around the cut sites
+    (``offset_around_cut`` columns each side), built from the resident batch in HBM without a
+    read's text on the host and upper case, as ``summarize_pooled`` explains.
 
     Deliberate differences: an ``Expected_HDR`` row is refused unless ``allow_hdr``, as in
     ``summarize_pooled``; discovered regions carry no ``Expected_HDR``; there
@@ -746,6 +750,8 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
     from . import demux, quantify
     from .aligner import NeedleError
 
+    if alleles and reports is None:
+        raise ValueError("alleles=True fills the regions' reports: pass reports as well")
     if not isinstance(region_reads, ResidentRegionReads):
         raise TypeError("summarize_regions takes the resident reads of a packed call (extract_regions_resident)")
     if region_reads.closed:
@@ -790,7 +796,8 @@ def summarize_regions(rows: Sequence[dict], region_reads: ResidentRegionReads, a
              exclude_bp_from_left=exclude_bp_from_left, exclude_bp_from_right=exclude_bp_from_right,
              ignore_substitutions=ignore_substitutions, ignore_insertions=ignore_insertions,
              ignore_deletions=ignore_deletions, hide_mutations_outside_window_NHEJ=hide_mutations_outside_window_NHEJ),
-        on_group, hdrs if allow_hdr else None, float(hdr_perfect_alignment_threshold), reports)
+        on_group, hdrs if allow_hdr else None, float(hdr_perfect_alignment_threshold), reports, bool(alleles),
+        int(offset_around_cut))
     frame = demux.summary_frame([row["Name"] for row in rows], out, n_reads, skipped)
     return RegionSummary(out, frame, skipped, times, n_reads)
 
@@ -934,7 +941,8 @@ def region_sequences(fasta_path: str, regions: Sequence[Region]) -> List[str]:
 def _summary_main(args, bam: BamRecords, hdr_options: dict) -> int:
     """``--summary``: SAMPLES_QUANTIFICATION_SUMMARY.txt of the regions of a file (CRISPRessoWGS;
     --min-reads defaults to its 10) or of the discovered ones (genome mode: --min-reads as given).
-    With ``--reports`` also a ``CRISPResso_on_<name>`` folder per analysed region with a kept read."""
+    With ``--reports`` also a ``CRISPResso_on_<name>`` folder per analysed region with a kept read,
+    with ``--alleles`` the allele tables in it."""
     import os
 
     from . import demux
@@ -954,7 +962,9 @@ def _summary_main(args, bam: BamRecords, hdr_options: dict) -> int:
     refused: list = []
     writer = demux._folder_writer(args.out, folders, refused) if args.reports else None
     with res, GpuAligner(args.device) as aligner:
-        summary = summarize_regions(rows, res, aligner, min_reads=min_reads, reports=writer, **hdr_options)
+        tables = dict(alleles=True, offset_around_cut=20 if args.offset_around_cut_to_plot is None
+                      else args.offset_around_cut_to_plot) if args.alleles else {}
+        summary = summarize_regions(rows, res, aligner, min_reads=min_reads, reports=writer, **tables, **hdr_options)
     demux.write_summary(os.path.join(args.out, "SAMPLES_QUANTIFICATION_SUMMARY.txt"), summary.frame)
     for row, n in zip(rows, summary.n_reads):
         print(f"{row['Name']}\t{n}")
@@ -984,6 +994,11 @@ def build_parser():
     p.add_argument("--reports", action="store_true",
                    help="with --summary: write a CRISPResso_on_<name> folder per analysed region (editing frequencies, "
                         "effect vectors, size histograms), as CRISPRessoCompare reads them")
+    p.add_argument("--alleles", action="store_true",
+                   help="with --reports: also write Alleles_frequency_table.txt and, per sgRNA, "
+                        "Alleles_frequency_table_around_cut_site_for_<sgRNA>.txt into every folder (upper case)")
+    p.add_argument("--offset_around_cut_to_plot", type=int, default=None,
+                   help="with --alleles: the columns each side of the cut site in the around-cut tables (default 20)")
     p.add_argument("--reference-order", action="store_true",
                    help="with --discover: reads in the order the reference's sort leaves them (C locale)")
     p.add_argument("--out", required=True, help="output directory")
@@ -1019,6 +1034,10 @@ def main(argv=None) -> int:
     hdr_options = summary_options(p, args)
     if args.reports and not args.summary:
         p.error("--reports is used only with --summary")
+    if args.alleles and not args.reports:
+        p.error("--alleles is used only with --reports")
+    if args.offset_around_cut_to_plot is not None and not args.alleles:
+        p.error("--offset_around_cut_to_plot is used only with --alleles")
     if args.summary and not args.genome:
         p.error("--summary needs --genome, the regions' amplicons come from it")
     if args.summary and (args.by_reference or args.reference_order):

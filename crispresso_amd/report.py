@@ -7,14 +7,18 @@ Host code only: a :class:`GroupReport` holds one group's exact integers (``nws_s
 slots, the quantifier's totals over the kept reads, ``nws_histograms``' four size histograms),
 :func:`tables` makes the four histogram tables of :func:`crispresso_amd.quantify.run_summary` of
 them, :func:`write_report` the files CRISPRessoCompare and CRISPRessoPooledWGSCompare read
-(CRISPRessoCompareCORE.py:39-49) and the rest of the reference's text output that needs no read's
-text.  ``Alleles_frequency_table.txt``, the plots and the pickles are not written.
+(CRISPRessoCompareCORE.py:39-49) and the rest of the reference's text output.  With the callers'
+``alleles=True`` a report also carries the allele table and the tables around the cut sites, made
+from the resident batch without a read's text on the host (:mod:`crispresso_amd.alleles`;
+upper case, as the whole resident path is), and ``Alleles_frequency_table.txt`` and
+``Alleles_frequency_table_around_cut_site_for_<sgRNA>.txt`` are written too.  The plots and the
+pickles are not written.
 """
 from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Dict, Sequence
+from typing import Dict, Optional, Sequence
 
 import numpy as np
 
@@ -35,7 +39,11 @@ class GroupReport:
     pass over the kept reads (vectors, counters and the two frameshift histograms).  ``hist_ins``,
     ``hist_del``, ``hist_mut``: int64 ``[bins]``, the kept reads with that ``n_inserted``,
     ``n_deleted``, ``n_mutated``; ``hist_indel``: int64 ``[2 bins - 1]``, entry ``d + bins - 1``
-    the kept reads with ``n_inserted - n_deleted == d``."""
+    the kept reads with ``n_inserted - n_deleted == d``.  ``alleles``: the group's ``df_alleles``
+    (:func:`crispresso_amd.alleles.resident_allele_table`) or None; ``around_cut``: a list of
+    ``(sgRNA, cut_point, frame)``, one per pair of ``zip(guides, cut_points)`` as the reference
+    pairs them (CRISPRessoCORE.py:3643-3654: a guide with two matches gets the file of its first
+    cut point only, and later guides get the cut points that follow), or None."""
 
     name: str
     amplicon: str
@@ -49,6 +57,8 @@ class GroupReport:
     hist_indel: np.ndarray
     has_coding_seq: bool = False
     has_expected_hdr: bool = False
+    alleles: Optional["pd.DataFrame"] = None
+    around_cut: Optional[list] = None
 
     @property
     def n_total(self) -> int:
@@ -109,7 +119,10 @@ def write_report(folder: str, report: GroupReport) -> list:
     input and after preprocessing are both the group's size), the NHEJ and combined effect
     vectors, the two average-size vectors and the four histogram tables.  With a coding sequence
     the frameshift and splice-site counts and the noncoding vectors; with an Expected_HDR the HDR
-    and mixed vectors.  A report without a kept read raises :class:`ReportError`: the reference
+    and mixed vectors.  With ``report.alleles`` Alleles_frequency_table.txt (the columns through
+    ``%Reads``, no index; CORE:3835), and for every entry of ``report.around_cut``
+    Alleles_frequency_table_around_cut_site_for_<sgRNA>.txt (the index kept; CORE:3649); with
+    both None not a byte more than without them.  A report without a kept read raises :class:`ReportError`: the reference
     stops such a run (CORE:2027)."""
     n_total = report.n_total
     if n_total == 0:
@@ -161,4 +174,27 @@ def write_report(folder: str, report: GroupReport) -> list:
         vector("effect_vector_insertion_HDR", v["effect_vector_insertion_hdr"])
         vector("effect_vector_deletion_HDR", v["effect_vector_deletion_hdr"])
         vector("effect_vector_substitution_HDR", v["effect_vector_mutation_hdr"])
+    if report.alleles is not None:                  # CORE:3835
+        report.alleles.loc[:, :"%Reads"].to_csv(os.path.join(folder, ALLELES_FILE), sep="\t", header=True, index=None)
+        written.append(ALLELES_FILE)
+    for sgrna, _, frame in report.around_cut or ():  # CORE:3643-3654 (a guide met twice writes its file twice)
+        name = around_cut_file(sgrna)
+        frame.to_csv(os.path.join(folder, name), sep="\t", header=True)
+        if name not in written:
+            written.append(name)
     return written
+
+
+ALLELES_FILE = "Alleles_frequency_table.txt"
+
+
+def around_cut_file(sgrna: str) -> str:
+    return "Alleles_frequency_table_around_cut_site_for_%s.txt" % sgrna
+
+
+def guide_cut_pairs(guide_seq: Optional[str], cut_points: Sequence[int]) -> list:
+    """``zip(sg_rna_sequences, cut_points)`` as the reference pairs them (CORE:1290-1341,
+    3643): the guides are the comma-separated, upper-cased sgRNAs in the order given, the cut
+    points every match of every guide in that order; the shorter list ends the pairing."""
+    guides = [g for g in (guide_seq or "").strip().upper().split(",")] if guide_seq else []
+    return list(zip(guides, [int(c) for c in cut_points]))

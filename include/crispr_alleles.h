@@ -109,12 +109,65 @@ int nwa_windows_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_o
 int nwa_windows_fetch(const nwa_ctx* c, int32_t k, uint8_t* win, int32_t* win_len, int64_t* first, int64_t* count,
                       uint8_t* unedited, int32_t* group_of_read);
 
-/* Records of the last nwa_windows_device that went through the exact host path, over its cut points. */
+/* nwa_windows_device with the keep flags and the results in HBM: d_keep (uint8 [n], non-zero
+ * = kept, or NULL) and d_results (nwq_read [n]) are DEVICE arrays, as a resident summary leaves
+ * them (nws_flags, nwq_run_device_ops); the kept count comes from a device reduction and
+ * cls == 0 is tested on the device.  tag stays a HOST array or NULL.  Everything else (limits,
+ * NW_E_UNSUPPORTED cases, the no-cut report, nwa_windows_fetch) as nwa_windows_device: the two
+ * share one body.  Synchronous. */
+int nwa_windows_resident(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_off, const void* d_stats,
+                         const uint8_t* d_reads, const int64_t* d_offsets, int64_t reads_bias, int64_t n, int32_t awidth,
+                         const char* amplicon, int32_t amp_len, const int32_t* cut_points, int32_t n_cuts, int32_t offset,
+                         const uint8_t* d_keep, const int32_t* tag, const int32_t* d_results, int32_t want_group_of_read,
+                         int64_t* n_groups, int64_t* n_no_cut, int64_t* first_no_cut);
+
+/* Records of the last nwa_windows_device / nwa_windows_resident that went through the exact host
+ * path, over its cut points. */
 int64_t nwa_windows_collided(const nwa_ctx* c);
 
 /* Device time of the last nwa_windows_device: ms[0] extract, ms[1] grouping (hash .. compaction),
  * ms[2] unedited + gather.  A diagnostic (scripts/bench_around_cut.py). */
 int nwa_windows_times(const nwa_ctx* c, float* ms);
+
+/* The allele table's rows (CRISPRessoCORE.py:2923-2946) of a device-resident ops-mode batch
+ * whose keep flags and results are in HBM as well: no read's text is needed on the host
+ * (crispresso_amd/csrc/nw_allele_rows.hip).
+ *
+ * d_ops .. reads_bias, n, awidth, amplicon (HOST bytes, any; copied to the device), amp_len: as
+ * nwa_windows_device takes them.  d_keep: DEVICE uint8 [n], non-zero = kept, or NULL (all
+ * kept).  d_results: DEVICE nwq_read [n].
+ *
+ * The kept reads are grouped by their bytes exactly as nwa_group_device groups them (no tag):
+ * groups in order of first appearance; reads whose hash collided go through the exact host path.
+ * For the first read of every group one wavefront walks the read's runs and writes the
+ * aligned-read row and the reference row, cut to cols = min(aln_len, awidth) columns, into a
+ * DEVICE buffer [groups][2][*row_stride], zero-padded past cols; *row_stride is the largest cols
+ * rounded up to 16 (at least 16).  The same launch gathers cols, the group's first read and
+ * size, and the first read's nwq_read.  The device bytes are upper case, as the whole resident
+ * path is.
+ *
+ * NW_E_INVALID (nothing kept for nwa_table_fetch, *n_groups = 0) when the runs of a group's
+ * first read do not end at the end of its bytes and of the amplicon, hold an unknown run type or
+ * fewer columns than cols (nw_expand_ops_subset refuses the same runs); such a byte is never
+ * loaded.  A kept read without a byte and without a run has cols = 0 and is not an error.
+ * n == 0 or nothing kept: zero groups.  The result is a function of the input alone.  Kept on
+ * the context until its next nwa_table_device.  Synchronous. */
+int nwa_table_device(nwa_ctx* c, const uint32_t* d_ops, const int64_t* d_ops_off, const void* d_stats,
+                     const uint8_t* d_reads, const int64_t* d_offsets, int64_t reads_bias, int64_t n, int32_t awidth,
+                     const char* amplicon, int32_t amp_len, const uint8_t* d_keep, const int32_t* d_results,
+                     int64_t* n_groups, int32_t* row_stride);
+
+/* The groups of the last nwa_table_device into HOST arrays (any may be NULL): rows uint8
+ * [groups][2][row_stride] (the aligned-read row, then the reference row), cols int32, first /
+ * count int64, results int32 [groups][4] (the first read's nwq_read). */
+int nwa_table_fetch(nwa_ctx* c, uint8_t* rows, int32_t* cols, int64_t* first, int64_t* count, int32_t* results);
+
+/* Reads of the last nwa_table_device that went through the exact host path. */
+int64_t nwa_table_collided(const nwa_ctx* c);
+
+/* Device time of the last nwa_table_device: ms[0] grouping (hash .. compaction), ms[1] the column
+ * and row kernels.  A diagnostic (scripts/bench_pooled_alleles.py). */
+int nwa_table_times(const nwa_ctx* c, float* ms);
 
 #ifdef __cplusplus
 }
